@@ -11,6 +11,11 @@ the fixed decode budget ceil(3.5 tok/s x 92 s) = 322 tokens, EOS ignored
 (random init, reference tensor names/shapes) unless $QASR_MODEL is set.
 PCM is staged in HBM before the timed region (qasr_stage_audio).
 
+A plain run sets up, warms up, times --steps steps, writes the last step's
+results (--dump-outputs DIR) and prints the JSON line.  --full adds the legs
+that take runs of their own after the timed region: the secondary kernels'
+roofline probes, the utterance set (configs[3]) and the CPU baseline.
+
 Multi-GPU: one process per GPU (torchrun); each rank transcribes its own clips
 (weak scaling, no data-path collective); barrier + max-over-ranks timing via
 torch.distributed (RCCL); value = all ranks' audio-seconds / max wall time.
@@ -53,7 +58,18 @@ def parse():
     ap.add_argument("--batch", type=int, default=1, help="clips per GPU per step")
     ap.add_argument("--tok-rate", type=float, default=3.5, help="decode budget tokens per audio second")
     ap.add_argument("--model", default=os.environ.get("QASR_MODEL", ""))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need, each in runs of its own: "
+                         "the secondary kernels' roofline probes (roofline_other), the utterance_set leg (configs[3], "
+                         "--set-*) and the CPU baseline (cpu_baseline, --cpu-*)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float64): tokens.npy, the greedy token ids [clips, budget] (--utterances: "
+                         "[utterances, longest budget], padded with -1, and budgets.npy); without --utterances, "
+                         "--pipeline align adds align_times.npy, every word's start and end in seconds, clip after "
+                         "clip, and align_words.npy, the words per clip.  Inputs are seeded: equal arguments give equal "
+                         "inputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample-seconds", type=float, default=10.0)
     ap.add_argument("--probe-layer", type=int, default=14, help="decoder layer whose fused launches are probed")
     ap.add_argument("--fa-exact-decode", type=int, default=None, choices=(0, 1),
@@ -81,7 +97,7 @@ def parse():
                          "aligner document from the last timed pass to this JSON file (tests/test_gpu_api.py checks it "
                          "against the oracle)")
     ap.add_argument("--set-utterances", type=int, default=1000,
-                    help="the default run's utterance_set leg (configs[3], SURVEY.md §8(d)): N fixed-length utterances "
+                    help="--full's utterance_set leg (configs[3], SURVEY.md §8(d)): N fixed-length utterances "
                          "through the dynamic queue into each GPU's continuous-batching stream, strong scaling over the "
                          "ranks (0: skip)")
     ap.add_argument("--set-seconds", type=float, default=30.0)
@@ -102,6 +118,17 @@ def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy in float64 (token ids
+    and counts are exact there), 64 MB at the most in all"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def launch_ranks(n: int) -> int:
@@ -501,6 +528,12 @@ def utterance_main(args, m, rank, local, world, dist, model_path):
     toks = res["tokens"]
     assert len(toks) == len(utts), (len(toks), len(utts))
     assert all(len(toks[i]) == qd.budget(n, args.tok_rate) for i, (_, n) in enumerate(utts)), "decode budget not met"
+    if args.dump_outputs:   # the last timed pass's token ids, utterance by utterance
+        buds = [len(toks[i]) for i in range(len(utts))]
+        tk = np.full((len(utts), max(buds)), -1.0)
+        for i, b in enumerate(buds):
+            tk[i, :b] = toks[i]
+        dump_outputs(args.dump_outputs, {"tokens": tk, "budgets": buds})
     audio = res["audio_s"] * args.steps
     out = {
         "metric": "RTFx (audio-sec/wall-sec) + decode tokens/sec, Qwen3-ASR-0.6B " + ("q8_0" if args.q8 else "f16") +
@@ -846,11 +879,14 @@ def main():
         need = max(qasr.align_prompt_len(n, len(am.align_tokenize(t)[0])) for t in texts)
         actx = qasr.Context(am, max_batch=min(args.batch, args.align_batch), max_ctx=need + 8)
 
-    def align_all():   # the step's clips, align_batch per aligner pass
+    def align_all():   # the step's clips, align_batch per aligner pass -> their documents
         ab = min(args.batch, args.align_batch)
+        out = []
         for k in range(0, len(clips), ab):
             docs, _ = actx.align_json_batch(clips[k:k + ab], texts[k:k + ab])
             assert len(docs) == len(clips[k:k + ab])
+            out += docs
+        return out
     if args.fa_exact_decode is not None:
         ctx.set_option("fa_exact_decode", args.fa_exact_decode)
     fx = ctx.get_option("fa_exact_decode")
@@ -868,7 +904,7 @@ def main():
         ctx.set_probe(2)   # the dominant kernel: layer probe_layer's QKV + attention (+ o-proj) launch
     barrier()
     t0 = time.perf_counter()
-    res = None
+    res, docs = None, []
     tm = {"mel": 0.0, "encode": 0.0, "prefill": 0.0, "decode": 0.0}
     for _ in range(args.steps):
         res = ctx.run(ntok, ignore_eos=True)   # synchronises its stream before returning
@@ -878,7 +914,7 @@ def main():
         tm["decode"] += res.timings.t_decode_ms
         if actx:
             ta = time.perf_counter()
-            align_all()
+            docs = align_all()
             tm["align"] = tm.get("align", 0.0) + (time.perf_counter() - ta) * 1e3
     barrier()
     dt = time.perf_counter() - t0
@@ -889,19 +925,26 @@ def main():
         dt = float(t.item())
     probe = (*ctx.get_probe(), *ctx.get_probe_device()) if not args.no_probe else None
     extra = {}
-    if not args.no_probe:   # untimed: one more run per secondary kernel
+    if args.full and not args.no_probe:   # untimed: one more run per secondary kernel
         for kind in (3, 1):
             ctx.set_probe(kind)
             ctx.run(ntok, ignore_eos=True)
             extra[kind] = (*ctx.get_probe(), *ctx.get_probe_device())
         ctx.set_probe(0)
     assert all(len(x) == ntok for x in res.tokens), "decode budget not met"
+    if args.dump_outputs and rank == 0:   # the last timed step's results, as ctx.run / align_json_batch returned them
+        arrays = {"tokens": res.tokens}
+        if actx:
+            arrays["align_words"] = [len(d["words"]) for d in docs]
+            arrays["align_times"] = [v for d in docs for w in d["words"] for v in (w["start"], w["end"])]
+        dump_outputs(args.dump_outputs, arrays)
     attn_path = ctx.get_option("attn_path")
     # the configs[1] context's HIP stream goes before the utterance set's contexts take theirs: the set
     # contexts + the default stream (+ RCCL's at N > 1) share the box's four hardware queues
     # (GPU_MAX_HW_QUEUES); with it open, three set contexts gave 8590 RTFx against 8768 for two
     ctx.close()
-    uset = utterance_set_leg(args, m, rank, local, world, dist) if args.set_utterances > 0 and not actx else None
+    uset = (utterance_set_leg(args, m, rank, local, world, dist)
+            if args.full and args.set_utterances > 0 and not actx else None)
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -941,7 +984,8 @@ def main():
                      if v[1]})
         top = max((k for k in ents if k != 1), key=lambda k: ents[k]["avg_launch_us"])
         out["roofline"] = ents.pop(top)
-        out["roofline_other"] = list(ents.values())
+        if args.full:
+            out["roofline_other"] = list(ents.values())
     # the north-star fractions of the two stages: encoder
     # FLOPs against the dense fp16 MFMA peak, decode bytes against HBM
     enc_s = tm["encode"] / args.steps / 1e3
@@ -957,7 +1001,7 @@ def main():
                              "frac": round(db / dec_s / 1e9 / HBM_PEAK_GBS, 4), "bytes_per_step": db}
     if uset:
         out["utterance_set"] = uset
-    if N == 1 and world == 1 and not args.no_cpu_baseline:
+    if args.full and N == 1 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model_path, args.cpu_sample_seconds, args.tok_rate, args.cpu_threads,
                                            args.seconds, ntok)
     print(json.dumps(out), flush=True)

@@ -150,6 +150,34 @@ def test_bench_utterance_driver(gpu, queue, pipeline, n, tmp_path):
         assert st["clips"] == n and 0 < st["slot_utilisation"] <= 1
 
 
+def test_bench_plain_run_dumps_its_outputs(gpu, tiny_gguf, tmp_path):
+    """A plain bench.py run (tiny model, one 3 s clip): --steps sets the timed
+    steps, the line carries ms_per_step and none of --full's legs, and
+    --dump-outputs writes the last timed step's token ids as float64 -- the
+    ids the API returns for the same seeded clip."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--seconds", "3", "--model", tiny_gguf, "--probe-layer", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(3.0 / (line["ms_per_step"] / 1e3), rel=1e-3)
+    assert not {"utterance_set", "cpu_baseline", "roofline_other"} & set(line)
+    assert sorted(os.listdir(out)) == ["tokens.npy"]
+    got = np.load(out / "tokens.npy")
+    ntok = 11   # ceil(3.5 tok/s x 3 s)
+    assert got.dtype == np.float64 and got.shape == (1, ntok)
+    m = qasr.Model(tiny_gguf)
+    c = qasr.Context(m, max_batch=1, max_ctx=256)
+    try:
+        ref = c.transcribe([qasr.synth_pcm(1000, 3 * SR)], max_tokens=ntok, ignore_eos=True).tokens
+    finally:
+        c.close()
+        m.close()
+    assert got.tolist() == [[float(t) for t in ref[0]]]
+
+
 def test_probe_stride_samples_steps(gpu, tiny_gguf):
     """the bench's roofline probe (qasr_set_probe) with probe_stride = 4 times
     every 4th decode step only (HIP events and the device-clock record), and

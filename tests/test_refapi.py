@@ -1,9 +1,10 @@
 """The reference's own driver programs against this repo's component API.
 
-tools/refapi/Makefile compiles 17 of the reference's tests/*.cpp -- every one
+oracle/refapi/Makefile compiles 17 of the reference's tests/*.cpp -- every one
 that includes only the component headers (mel_spectrogram.h, audio_encoder.h,
 text_decoder.h, audio_injection.h) -- in place and unchanged, against
-include/ + libqasr.so, in the build container.  Here:
+include/ + libqasr.so, into oracle/_ref/refapi where the reference tree
+exists.  Here:
 
 * (CPU) every one of them compiled and linked, and test_injection.cpp (host
   code only) passes its own checks;
@@ -30,7 +31,7 @@ import oracle_py as op
 import qasr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "tools", "refapi", "_out")
+OUT = os.path.join(ROOT, "oracle", "_ref", "refapi")
 REF = "/root/reference/tests"
 DRIVERS = ["test_decoder_simple", "test_decoder_last_pos", "test_decoder_no_audio", "test_encoder",
            "test_attention_compare", "test_conv_no_chunk", "test_conv_only", "test_decoder", "test_decoder_50",
@@ -44,13 +45,15 @@ def _npy(path, a):
 
 
 def _run(args, cwd, timeout=240):
-    env = dict(os.environ)
+    # (the drivers find libqasr.so relative to themselves; the path also covers binaries linked before a move)
+    lib = os.path.join(ROOT, "qwen3-asr.cpp_amd")
+    env = dict(os.environ, LD_LIBRARY_PATH=lib + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""))
     return subprocess.run(args, cwd=cwd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
 @pytest.mark.skipif(not os.path.isdir(REF), reason="the reference sources exist only in the build container")
 def test_reference_drivers_compile_against_component_api():
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "tools", "refapi")], capture_output=True, text=True, timeout=600)
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "refapi")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     for d in DRIVERS:
         assert os.path.isfile(os.path.join(OUT, d)), d
@@ -64,13 +67,13 @@ def test_reference_injection_driver(tmp_path):
 
 
 def _need(name):
-    """the driver binary: __graft_entry__.build() compiles them in the build
-    container (where /root/reference exists) and they travel with the tree,
-    so a missing one is a failure, not a skip"""
+    """the driver binary: __graft_entry__.build() compiles them where the
+    reference tree exists, into oracle/_ref/refapi, which goes with the tree
+    to the GPU machine, so a missing one is a failure, not a skip"""
     exe = os.path.join(OUT, name)
     if not os.path.isfile(exe):
-        pytest.fail(f"tools/refapi/_out/{name} missing: run __graft_entry__.build() (make -C tools/refapi) in the "
-                    "build container before the GPU run")
+        pytest.fail(f"oracle/_ref/refapi/{name} missing: run __graft_entry__.build() (make -C oracle/refapi) where "
+                    "the reference tree exists before the GPU run")
     return exe
 
 

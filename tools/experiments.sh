@@ -22,6 +22,7 @@
 set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+QLOG=$(mktemp)   # qffn / qffn2: the bench line being read
 case "${1:-}" in
 b64prof)
 export QASR_NO_GRAPH=1
@@ -141,15 +142,16 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_full.py -x -v --timeout 300
 rc=$?; tail -15 gpurun_out/qf_t.log; [ $rc -ne 0 ] && exit $rc
 for cfg in "0 20 10" "1 20 10" "1 10 10" "1 30 10" "1 20 4" "1 20 20"; do
   set -- $cfg
-  QASR_QKV_FFN=$1 QASR_QFFN_DELAY=$2 QASR_QFFN_POLL_DELAY=$3 timeout -k 10 150 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/qf_b.log 2>&1 || exit 1
-  python3 -c "import json,sys; d=json.loads([l for l in open('gpurun_out/qf_b.log') if l.startswith('{')][-1]); print('qkv_ffn=$1 delay=$2 poll=$3', d['value'], d['stage_ms_per_step_rank0']['decode'], d['roofline']['avg_launch_us'], d['roofline_other'][0]['avg_launch_us'])"
+  # (--full: roofline_other's FFN launch is probed in a run of its own)
+  QASR_QKV_FFN=$1 QASR_QFFN_DELAY=$2 QASR_QFFN_POLL_DELAY=$3 timeout -k 10 150 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --set-utterances 0 > "$QLOG" 2>&1 || exit 1
+  python3 -c "import json,sys; d=json.loads([l for l in open('$QLOG') if l.startswith('{')][-1]); print('qkv_ffn=$1 delay=$2 poll=$3', d['value'], d['stage_ms_per_step_rank0']['decode'], d['roofline']['avg_launch_us'], d['roofline_other'][0]['avg_launch_us'])"
 done
 ;;
 qffn2)
 for cfg in "0 0" "1 0" "1 64" "0 64"; do
   set -- $cfg
-  QASR_QKV_FFN=$1 QASR_ATT_SPL1=$2 QASR_QFFN_DELAY=30 timeout -k 10 150 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/qf_b.log 2>&1 || exit 1
-  python3 -c "import json,sys; d=json.loads([l for l in open('gpurun_out/qf_b.log') if l.startswith('{')][-1]); print('qkv_ffn=$1 spl1=$2', d['value'], d['stage_ms_per_step_rank0']['decode'], d['roofline']['avg_launch_us'], d['roofline_other'][0]['avg_launch_us'])"
+  QASR_QKV_FFN=$1 QASR_ATT_SPL1=$2 QASR_QFFN_DELAY=30 timeout -k 10 150 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --set-utterances 0 > "$QLOG" 2>&1 || exit 1
+  python3 -c "import json,sys; d=json.loads([l for l in open('$QLOG') if l.startswith('{')][-1]); print('qkv_ffn=$1 spl1=$2', d['value'], d['stage_ms_per_step_rank0']['decode'], d['roofline']['avg_launch_us'], d['roofline_other'][0]['avg_launch_us'])"
 done
 for q in 0 1; do
   QASR_DEV_TRACE=gpurun_out/tr_q$q.bin QASR_DEV_TRACE_LAYER=14 QASR_QKV_FFN=$q QASR_QFFN_DELAY=30 timeout -k 10 150 python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-probe > gpurun_out/qf_tr$q.log 2>&1 || exit 1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end measurement evidence -> $PROF_OUT (default gpurun_out/prof), copied
 # to profiles/<round>/ by hand:
-#   bench.json      the default bench.py line (configs[1])
+#   bench.json      the bench.py --full line (configs[1] with roofline_other, utterance_set, cpu_baseline)
 #   configs/*.json  the other BASELINE configs' lines (PROF_CONFIGS=1)
 #   stats/          rocprofv3 --kernel-trace --stats over bench.py (decode step
 #                   eager, QASR_NO_GRAPH=1: rocprofv3 7.2 faults inside
@@ -31,7 +31,7 @@ step() {  # step <name> <timeout_s> <cmd...>
     tail -3 "gpurun_out/$name.log" >&2
     if [ $rc -ne 0 ]; then echo "stopping after $name (rc=$rc)" >&2; exit $rc; fi
 }
-step bench 600 python -u bench.py $ARGS
+step bench 600 python -u bench.py --full $ARGS
 grep '^{"metric"' gpurun_out/bench.log > "$OUT/bench.json"
 if [ "${PROF_CONFIGS:-0}" = 1 ]; then
     mkdir -p "$OUT/configs"
