@@ -36,6 +36,10 @@
  *   qasr_align_tokenize <- ForcedAligner::tokenize_with_timestamps :1564-1609
  *   qasr_model_load_korean_dict <- ForcedAligner::load_korean_dict :1543-1562
  *   qasr_fix_timestamps <- ForcedAligner::fix_timestamp_classes :1183-1265
+ *   qasr_get_step_logprobs, qasr_get_logprobs, qasr_stream_logprobs
+ *       no reference counterpart: sample_greedy keeps the token id and drops
+ *       the logits; these return log softmax(logits)[argmax] of every greedy
+ *       token (context option "token_logprobs")
  *
  * Conventions (mirroring the reference's):
  *   - return value: 0 = OK, nonzero = error; message via qasr_last_error().
@@ -257,6 +261,29 @@ int qasr_ctx_get_option(const qasr_ctx *c, const char *name, int *value);
  * [max_batch][hidden] residual stream, "act" fp16 [max_batch][ffn] SwiGLU
  * output, "qkv" fp32 [max_batch][q+k+v], "att" fp16 [max_batch][n_head*128] */
 int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64_t bytes);
+
+/* ---- token log-probabilities (no reference counterpart) -------------------- */
+/* Context option "token_logprobs" [QASR_TOKEN_LOGPROBS], default 0: every
+ * greedy step also computes log softmax(logits)[token] of the token it chose,
+ * over the whole vocabulary row, on the device (decode batches of 9..128 rows
+ * of 1024-wide f16 models: inside the one-launch LM head; every other path:
+ * one more small launch over the fp32 logits).  Tokens are the same with the
+ * option on or off.  With it off, or before a call of the kind named has run
+ * with it on, the three calls return QASR_ERR_STATE; a null or short buffer is
+ * QASR_ERR_ARG.
+ *   qasr_get_step_logprobs: the value of each row's argmax of the last
+ *       qasr_prefill* / qasr_decode_step (B >= that call's B; B values written)
+ *   qasr_get_logprobs: the last qasr_run / qasr_run_staged /
+ *       qasr_transcribe_batch; out [B][max_tokens] row-major, row b's first
+ *       n_tokens[b] entries aligned with its returned tokens (a popped trailing
+ *       EOS drops its value too); B and max_tokens at least the run's batch
+ *       and longest row
+ *   qasr_stream_logprobs: only inside a qasr_sink_fn call of qasr_run_stream*
+ *       with status 0: the values of the clip being delivered (one per token
+ *       passed to the sink); returns their count (>= 0), or minus an error code */
+int qasr_get_step_logprobs(qasr_ctx *c, float *out, int B);
+int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens);
+int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap);
 
 /* Per-token callback (Qwen3ASR::set_progress_callback, src/qwen3_asr.cpp:255-291):
  * called synchronously on the caller's thread after every greedy token of

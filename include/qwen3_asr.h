@@ -26,6 +26,9 @@ struct transcribe_params {
     int32_t n_threads = 4;            // accepted for API compatibility (no host threads on the hot path)
     bool print_progress = false;
     bool print_timing = true;
+    // MI355X addition (trailing, default off): also return every token's log-probability
+    // (context option "token_logprobs" of qasr_capi.h; no reference counterpart)
+    bool token_logprobs = false;
 };
 
 // src/qwen3_asr.h:37-49
@@ -39,6 +42,9 @@ struct transcribe_result {
     int64_t t_encode_ms = 0;
     int64_t t_decode_ms = 0;   // prefill + greedy loop, as the reference's decode_greedy
     int64_t t_total_ms = 0;
+    // MI355X addition (trailing): with transcribe_params::token_logprobs, log softmax(logits)[token]
+    // of every entry of tokens (same length); empty otherwise
+    std::vector<float> token_logprobs;
 };
 
 using progress_callback_t = std::function<void(int tokens_generated, int max_tokens)>;
@@ -86,6 +92,7 @@ public:
 private:
     transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params);
     bool ensure_ctx(int batch, int n_ctx);
+    bool set_logprobs(bool on);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

@@ -107,6 +107,44 @@ __device__ __forceinline__ unsigned long long argmax_key(float v, int idx) {
     return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (uint32_t)idx);
 }
 __device__ __forceinline__ int argmax_key_idx(unsigned long long k) { return (int)(0xffffffffu - (uint32_t)(k & 0xffffffffu)); }
+// the winning value of an argmax key (its upper 32 bits, argmax_key's order undone)
+__device__ __forceinline__ float argmax_key_val(unsigned long long k) {
+    const uint32_t u = (uint32_t)(k >> 32);
+    return __uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u);
+}
+
+// log-sum-exp of a logit row as a running (m, s) pair: m the largest value so
+// far, s = sum exp(v - m) over the values so far; the empty pair is (-inf, 0).
+// One exp a value.  Token log-probabilities (option token_logprobs):
+// logprob(argmax) = logit_max - (m + log s).
+// The exp is the hardware one (v_exp_f32 of x * log2(e), x <= 0): its error
+// relative to the term is ~1e-7 (1 + |x|), and the terms that matter to s have
+// small |x| -- measured against float64 over the rows' own logits: 4e-7 at most
+// (tests/test_gpu_logprobs*.py, bar 2e-5); the OCML expf cost the one-launch
+// LM head 4x the VALU work per logit.
+__device__ __forceinline__ float lse_exp(float x) { return __expf(x); }
+__device__ __forceinline__ void lse_add(float &m, float &s, float v) {
+    const float e = lse_exp(-fabsf(v - m));   // (m = -inf: e = 0)
+    s = v > m ? s * e + 1.0f : s + e;
+    m = fmaxf(m, v);
+}
+// (m, s) <- the pair over both sets; the same bits whichever side is `this`
+__device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2) {
+    const float mn = fmaxf(m, m2);
+    const float a = m == mn ? s : s * lse_exp(m - mn);
+    const float b = m2 == mn ? s2 : s2 * lse_exp(m2 - mn);
+    s = a + b;
+    m = mn;
+}
+__device__ __forceinline__ unsigned long long lse_pack(float m, float s) {
+    return ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)__float_as_uint(m);
+}
+__device__ __forceinline__ float lse_pack_m(unsigned long long p) { return __uint_as_float((uint32_t)p); }
+__device__ __forceinline__ float lse_pack_s(unsigned long long p) { return __uint_as_float((uint32_t)(p >> 32)); }
+// log-probability of the row's largest logit vmax given the row's (m, s)
+__device__ __forceinline__ float lse_logprob(float vmax, float m, float s) {
+    return (float)((double)vmax - ((double)m + log((double)s)));
+}
 
 // non-contracted fp32 ops (ggml computes these as separate ops, each rounded)
 __device__ __forceinline__ float fmul_rn(float a, float b) { return __fmul_rn(a, b); }

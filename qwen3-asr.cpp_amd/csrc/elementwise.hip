@@ -242,6 +242,48 @@ void launch_argmax_finish(const unsigned long long *amax, int B, int32_t *ids, i
     hipLaunchKernelGGL(argmax_finish_kernel, dim3(1), dim3(256), 0, s, amax, B, ids, hist, hist_stride, step);
 }
 
+// ------------------------------------------------------- token log-probability
+// One workgroup a row.  Thread t folds columns 4 (t + 1024 i) .. + 3 in order
+// into its own (m, s) pair (dev_common.h lse_add), the wave's 64 pairs merge by
+// xor-shuffles (32 .. 1), the 16 wave pairs through LDS in wave order: a fixed
+// order, so a row's value depends on its logits alone.
+__global__ __launch_bounds__(1024) void token_logprob_kernel(const float *__restrict__ logits, int ld, int n_valid,
+                                                              const int32_t *__restrict__ tok, const int *__restrict__ step,
+                                                              float *__restrict__ lp_out, float *__restrict__ lp_hist,
+                                                              int hist_stride) {
+    __shared__ float wm[16], ws[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float *row = logits + (long)b * ld;
+    float m = -INFINITY, s = 0.f;
+    const int n4 = (ld & 3) ? 0 : n_valid >> 2;   // float4 columns (rows 16-B aligned), then the tail
+    for (int i = tid; i < n4; i += 1024) {
+        const float4 v = *(const float4 *)(row + 4 * i);
+        lse_add(m, s, v.x);
+        lse_add(m, s, v.y);
+        lse_add(m, s, v.z);
+        lse_add(m, s, v.w);
+    }
+    for (int i = 4 * n4 + tid; i < n_valid; i += 1024) lse_add(m, s, row[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if (lane == 0) { wm[wid] = m; ws[wid] = s; }
+    __syncthreads();
+    if (tid == 0) {
+        m = wm[0]; s = ws[0];
+        for (int w = 1; w < 16; w++) lse_merge(m, s, wm[w], ws[w]);
+        const float lp = lse_logprob(row[tok[b]], m, s);
+        lp_out[b] = lp;
+        if (lp_hist) lp_hist[(long)b * hist_stride + *step] = lp;
+    }
+}
+
+void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const int32_t *tok, const int *step, float *lp_out,
+                          float *lp_hist, int hist_stride, hipStream_t s) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(1024), 0, s, logits, ld, n_valid > 0 && n_valid < ld ? n_valid : ld,
+                       tok, step, lp_out, lp_hist, hist_stride);
+}
+
 // dst row r = src row idx[r] (fp32 rows of D floats, 16-B lanes)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, const int *__restrict__ idx, int rows, int D,
                                                           float *__restrict__ dst) {

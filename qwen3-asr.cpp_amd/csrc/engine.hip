@@ -137,6 +137,16 @@ struct qasr_ctx {
     uint16_t *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xh = nullptr;
     unsigned long long *d_amax = nullptr;
     int max_splits = 0, hist_cap = 0;
+    // option token_logprobs: the last step's log-probabilities [B], their history parallel to d_hist
+    // (stride hist_cap, the index of the token they belong to), the one-launch LM head's per-workgroup
+    // (m, s) partials [lmhead_grid()][128]
+    float *d_lp = nullptr, *d_lphist = nullptr;
+    unsigned long long *d_lppart = nullptr;
+    int lp_step_B = 0;             // rows of the last qasr_prefill* / qasr_decode_step with the option on (0: none)
+    std::vector<float> lp_run;     // the last qasr_run's values [lp_run_B][lp_run_T], aligned with its tokens
+    std::vector<int> lp_run_n;     // ... and how many per row
+    int lp_run_B = 0, lp_run_T = 0;
+    const std::vector<float> *lp_sink = nullptr;   // inside a qasr_sink_fn call: the delivered clip's values
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -242,6 +252,7 @@ static const std::vector<FuseOption> &fuse_options() {
         {"live_prefix", "QASR_LIVE_PREFIX", &FuseCfg::live_prefix},
         {"staged_wrap", "QASR_STAGED_WRAP", &FuseCfg::staged_wrap},
         {"poison_scratch", "QASR_POISON_SCRATCH", &FuseCfg::poison},
+        {"token_logprobs", "QASR_TOKEN_LOGPROBS", &FuseCfg::token_logprobs},
     };
     return v;
 }
@@ -781,7 +792,10 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
         (rc = dev_alloc(c.get(), (void **)&c->d_done, 4)) || (rc = dev_alloc(c.get(), (void **)&c->d_err, 4)) ||
         (rc = dev_alloc(c.get(), (void **)&c->d_pstamp, (size_t)max_ctx * kStampRec * 8)) ||
         (rc = dev_alloc(c.get(), (void **)&c->d_logits, (size_t)B * hp.vocab * 4)) ||
-        (rc = dev_alloc(c.get(), (void **)&c->d_amax, (size_t)B * 8)))
+        (rc = dev_alloc(c.get(), (void **)&c->d_amax, (size_t)B * 8)) ||
+        (rc = dev_alloc(c.get(), (void **)&c->d_lp, (size_t)B * 4)) ||
+        (rc = dev_alloc(c.get(), (void **)&c->d_lphist, (size_t)B * max_ctx * 4)) ||
+        (rc = dev_alloc(c.get(), (void **)&c->d_lppart, (size_t)lmhead_grid() * 128 * 8)))
         return rc;
     std::vector<int> slots(B);
     for (int b = 0; b < B; b++) slots[b] = b;
@@ -830,6 +844,11 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
             if (n == "poll_limit" && value <= 0) return fail(QASR_ERR_ARG, "poll_limit must be positive");
             c->fuse.*(o.field) = value;
             c->drop_graphs();   // captured steps hold the old launch configuration
+            if (o.field == &FuseCfg::token_logprobs) {   // nothing has run under the new setting
+                c->lp_step_B = c->lp_run_B = c->lp_run_T = 0;
+                c->lp_run.clear();
+                c->lp_run_n.clear();
+            }
             HIPCHK(hipSetDevice(c->m->device));   // arrival counters back to rest
             const int rc = reset_counters(c);
             if (rc) return rc;
@@ -1228,6 +1247,8 @@ static int run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const std::
     uint16_t *xl = c->d_xh;
     launch_rmsnorm_f16(x, H, c->plast.as<int>(), B, H, m->out_norm, hp.rms_eps, xl, s);
     launch_fill_u64(c->d_amax, B, 0ull, s);
+    const bool lp = c->fuse.token_logprobs != 0;   // the log-probabilities come from the fp32 logits
+    want_logits = want_logits || lp;
     if (B <= 8) {
         GemvArgs gv{};
         gv.xh = xl; gv.ldxh = H; gv.W = m->embd; gv.K = H; gv.N = hp.vocab; gv.M = B;
@@ -1241,6 +1262,7 @@ static int run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const std::
     }
     HIPCHK(hipMemsetAsync(c->d_step, 0, 4, s));
     launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
+    if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
     launch_fill_u64(c->d_amax, B, 0ull, s);   // zero at rest for the decode graph
     // decode state: next position = P_b, n_kv = P_b + 1 (the fed token's own key included)
     std::vector<int> pos(B), nkv(B);
@@ -1292,6 +1314,9 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     const bool skinny = B <= 8;
     // decode batches: the LM head as one launch (lmhead.hip's shape conditions)
     const bool lmh_one = !skinny && B <= 128 && c->fuse.lmh && H == 1024 && hp.vocab % 16 == 0;
+    // option token_logprobs: inside the one-launch LM head, else from the fp32 logits after the bookkeeping
+    const bool lp = c->fuse.token_logprobs != 0;
+    if (lp && !lmh_one) want_logits = true;
     const size_t layer_kv = (size_t)c->max_batch * hp.n_kv_head * c->max_ctx * 128;
     const int nl = step_layers(c);   // diagnostic layer cap
     // probed group (emitted alone): every launch in it folds its block times into one record
@@ -1458,6 +1483,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
             lm.pos = c->d_pos;
             lm.stamp = stamp;
             launch_gemv(EPI_ARGMAX, lm, s);
+            if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
         } else if (lmh_one) {   // norm + GEMM + argmax + bookkeeping in one launch (lmhead.hip)
             GemvArgs lm{};
             lm.x = x; lm.ldx = H; lm.norm_w = m->out_norm; lm.eps = hp.rms_eps; lm.W = m->embd; lm.K = H; lm.N = hp.vocab; lm.M = B;
@@ -1465,6 +1491,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
             lm.done = c->d_done; lm.tok_out = c->d_tok; lm.hist = c->d_hist; lm.hist_stride = c->hist_cap; lm.step = c->d_step;
             lm.pos = c->d_pos; lm.nkv = c->d_nkv;
             lm.stamp = stamp;
+            if (lp) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
             if (!launch_lmhead_batch(lm, s))   // (lmh_one mirrors its shape conditions: never expected)
                 return fail(QASR_ERR_STATE, "decode step: the batched LM head declined B = " + std::to_string(B));
         } else {
@@ -1479,6 +1506,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     if (r.in(2 + 2 * nl) && !skinny && !lmh_one) {   // bookkeeping (fused into the LM-head GEMV at batch <= 8)
         launch_step_advance(c->d_pos, c->d_nkv, c->d_step, B, s);
         launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
+        if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
         launch_fill_u64(c->d_amax, B, 0ull, s);   // re-arm (zero at rest)
     }
     return declined_check("decode step");
@@ -1856,6 +1884,7 @@ extern "C" int qasr_prefill(qasr_ctx *c, const int32_t *ids, const int *P, const
     if (logits_last) HIPCHK(hipMemcpyAsync(logits_last, c->d_logits, (size_t)B * c->m->hp.vocab * 4, hipMemcpyDeviceToHost, c->st));
     if (argmax) HIPCHK(hipMemcpyAsync(argmax, c->d_tok, B * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
+    c->lp_step_B = c->fuse.token_logprobs ? B : 0;
     return 0;
 }
 
@@ -1897,6 +1926,7 @@ static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, c
     if (logits_last) HIPCHK(hipMemcpyAsync(logits_last, c->d_logits, (size_t)B * c->m->hp.vocab * 4, hipMemcpyDeviceToHost, c->st));
     if (argmax) HIPCHK(hipMemcpyAsync(argmax, c->d_tok, B * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
+    c->lp_step_B = c->fuse.token_logprobs ? B : 0;
     return 0;
 }
 
@@ -1938,7 +1968,42 @@ extern "C" int qasr_decode_step(qasr_ctx *c, const int32_t *tok, const int *n_pa
     if (logits) HIPCHK(hipMemcpyAsync(logits, c->d_logits, (size_t)B * c->m->hp.vocab * 4, hipMemcpyDeviceToHost, c->st));
     if (argmax) HIPCHK(hipMemcpyAsync(argmax, c->d_tok, B * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
+    c->lp_step_B = c->fuse.token_logprobs ? B : 0;
     return check_dev_err(c);
+}
+
+extern "C" int qasr_get_step_logprobs(qasr_ctx *c, float *out, int B) {
+    if (!c || !out || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.token_logprobs) return fail(QASR_ERR_STATE, "option token_logprobs is off");
+    if (!c->lp_step_B) return fail(QASR_ERR_STATE, "no prefill or decode step has run with option token_logprobs on");
+    if (B < c->lp_step_B) return fail(QASR_ERR_ARG, "buffer shorter than the last step's batch");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipMemcpyAsync(out, c->d_lp, (size_t)c->lp_step_B * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+extern "C" int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens) {
+    if (!c || !out || B <= 0 || max_tokens <= 0) return fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.token_logprobs) return fail(QASR_ERR_STATE, "option token_logprobs is off");
+    if (!c->lp_run_B) return fail(QASR_ERR_STATE, "no run has finished with option token_logprobs on");
+    if (B < c->lp_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
+    for (int b = 0; b < c->lp_run_B; b++)
+        if (c->lp_run_n[b] > max_tokens) return fail(QASR_ERR_ARG, "buffer rows shorter than the last run's tokens");
+    for (int b = 0; b < c->lp_run_B; b++)
+        for (int k = 0; k < c->lp_run_n[b]; k++) out[(size_t)b * max_tokens + k] = c->lp_run[(size_t)b * c->lp_run_T + k];
+    return 0;
+}
+
+// (a count on success, so errors are minus the code, as qasr_align_json)
+extern "C" int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return -fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.token_logprobs) return -fail(QASR_ERR_STATE, "option token_logprobs is off");
+    if (!c->lp_sink) return -fail(QASR_ERR_STATE, "qasr_stream_logprobs is valid only inside a qasr_sink_fn call");
+    const int n = (int)c->lp_sink->size();
+    if (cap < n) return -fail(QASR_ERR_ARG, "buffer shorter than the clip's tokens");
+    for (int k = 0; k < n; k++) out[k] = (*c->lp_sink)[k];
+    return n;
 }
 
 extern "C" int qasr_stage_audio(qasr_ctx *c, const float *const *pcm, const int *n, int B) {
@@ -2074,6 +2139,19 @@ extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *to
     HIPCHK(hipEventSynchronize(c->ev[4]));
     if ((rc = check_dev_err(c))) return rc;
     if ((rc = probe_collect(c, B, steps))) return rc;
+    // option token_logprobs: columns 0 .. steps of the history parallel to d_hist (after the timed span)
+    const bool lp = c->fuse.token_logprobs != 0;
+    const int lp_cols = std::min(steps + 1, max_tokens);
+    std::vector<float> lph;
+    c->lp_run_B = 0;
+    if (lp) {
+        lph.resize((size_t)B * lp_cols);
+        HIPCHK(hipMemcpy2DAsync(lph.data(), (size_t)lp_cols * 4, c->d_lphist, (size_t)c->hist_cap * 4, (size_t)lp_cols * 4, B,
+                                hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        c->lp_run.assign((size_t)B * max_tokens, 0.f);
+        c->lp_run_n.assign(B, 0);
+    }
     if (c->profile_on) {   // the reference's QWEN3_TIMER sections (src/timing.h), device time
         auto add = [&](const char *name, hipEvent_t e0, hipEvent_t e1) -> int {
             float ms = 0.f;
@@ -2103,12 +2181,15 @@ extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *to
         int nt = 0;
         for (int k = 0; k <= steps && k < max_tokens; k++) {
             const int32_t tk = hist[(size_t)b * c->hist_cap + k];
+            if (lp) c->lp_run[(size_t)b * max_tokens + nt] = lph[(size_t)b * lp_cols + k];
             tokens[(size_t)b * max_tokens + nt++] = tk;
             if (!ignore_eos && tk == hp.eos_id) break;
         }
-        if (!ignore_eos && nt > 0 && tokens[(size_t)b * max_tokens + nt - 1] == hp.eos_id) nt--;
+        if (!ignore_eos && nt > 0 && tokens[(size_t)b * max_tokens + nt - 1] == hp.eos_id) nt--;   // (its value goes with it)
         n_tokens[b] = nt;
+        if (lp) c->lp_run_n[b] = nt;
     }
+    if (lp) { c->lp_run_B = B; c->lp_run_T = max_tokens; }
     if (t) {
         float a, b2, c2, d;
         (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
@@ -2157,6 +2238,7 @@ namespace {
 struct StreamSlot {
     int id = -1, P = 0, budget = 0;
     std::vector<int32_t> toks;
+    std::vector<float> lps;   // option token_logprobs: one per token
 };
 }  // namespace
 
@@ -2194,14 +2276,22 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
     std::vector<StreamSlot> sl(S);
     bool open = true;
     int rc;
+    const bool lp = c->fuse.token_logprobs != 0;
+    c->lp_sink = nullptr;
     // a finished clip: trailing EOS popped (src/qwen3_asr.cpp:298-300)
     auto deliver = [&](StreamSlot &x) {
         std::vector<int32_t> &t = x.toks;
-        if (!ignore_eos && !t.empty() && t.back() == hp.eos_id) t.pop_back();
+        if (!ignore_eos && !t.empty() && t.back() == hp.eos_id) {
+            t.pop_back();
+            if (lp) x.lps.pop_back();
+        }
+        if (lp) c->lp_sink = &x.lps;   // qasr_stream_logprobs, for the length of the call
         sink(user, x.id, 0, t.data(), (int)t.size());
+        c->lp_sink = nullptr;
         st.n_clips++;
         x.id = -1;
         x.toks.clear();
+        x.lps.clear();
     };
     auto reject = [&](int id, int code, const char *msg) {   // per-clip error: the message is qasr_last_error() inside sink
         fail(code, msg);
@@ -2271,7 +2361,9 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
             }
             if ((rc = run_prefill(c, pids, P, c->feats.as<float>(), ap, Nb, false, &slots))) return rc;
             std::vector<int32_t> first(R);
+            std::vector<float> first_lp(R);
             HIPCHK(hipMemcpyAsync(first.data(), c->d_tok, R * 4, hipMemcpyDeviceToHost, s));
+            if (lp) HIPCHK(hipMemcpyAsync(first_lp.data(), c->d_lp, R * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));   // (pcm host vector in flight until here)
             if ((rc = check_dev_err(c))) return rc;
             refilled = true;
@@ -2288,6 +2380,7 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                 x.P = P[r];
                 x.budget = budgets[r];
                 x.toks.assign(1, first[r]);
+                x.lps.assign(lp ? 1 : 0, first_lp[r]);
                 if (c->tok_cb) c->tok_cb(c->tok_cb_user, x.id, 1, first[r]);
                 if ((!ignore_eos && first[r] == hp.eos_id) || x.budget == 1) deliver(x);
             }
@@ -2295,6 +2388,7 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
     };
     std::vector<int> pos(S), nkv(S), tok(S);
     std::vector<int32_t> hist;
+    std::vector<float> lph;
     if ((rc = decode_graph(c, S, false, 0))) return rc;
     for (;;) {
         if ((rc = refill())) return rc;
@@ -2334,6 +2428,10 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
         hist.resize((size_t)S * chunk);
         // (a decode step advances d_step, then writes hist[step]: the chunk's tokens are columns 1..chunk)
         HIPCHK(hipMemcpy2DAsync(hist.data(), chunk * 4, c->d_hist + 1, (size_t)c->hist_cap * 4, chunk * 4, S, hipMemcpyDeviceToHost, s));
+        if (lp) {   // the same columns of the rows this chunk decoded (the slots past Bq hold earlier chunks' values)
+            lph.resize((size_t)S * chunk);
+            HIPCHK(hipMemcpy2DAsync(lph.data(), chunk * 4, c->d_lphist + 1, (size_t)c->hist_cap * 4, chunk * 4, Bq, hipMemcpyDeviceToHost, s));
+        }
         HIPCHK(hipStreamSynchronize(s));   // (the pos / nkv / tok host vectors in flight until here)
         if ((rc = check_dev_err(c))) return rc;
         st.t_decode_ms += ms_since(t0);
@@ -2346,6 +2444,7 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
             for (int k = 0; k < chunk; k++) {
                 const int32_t t = hist[(size_t)i * chunk + k];
                 x.toks.push_back(t);
+                if (lp) x.lps.push_back(lph[(size_t)i * chunk + k]);
                 st.live_steps++;
                 if (c->tok_cb) c->tok_cb(c->tok_cb_user, x.id, (int)x.toks.size(), t);
                 if ((!ignore_eos && t == hp.eos_id) || (int)x.toks.size() >= x.budget) {

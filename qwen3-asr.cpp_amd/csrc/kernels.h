@@ -137,6 +137,10 @@ struct GemvArgs {
     int *nkv;                            // launch_lmhead_batch: n_kv[b] += 1 with pos[b] (decode batches) or null
     int n_valid;                         // launch_lmhead_batch: columns >= n_valid never win; 0 = N
     int keep_step;                       // lmhead_batch_kernel: leave *step as it is (a first row-half launch)
+    // launch_lmhead_batch, token log-probabilities (all three or none; null = off, today's kernels):
+    // per-workgroup packed (m, s) partials [grid][128] (lmhead_grid() workgroups), the step's
+    // log-probability of each row's argmax [M], and its history parallel to hist (hist_stride)
+    unsigned long long *lp_part; float *lp_out; float *lp_hist;
 };
 void launch_gemv(int epi, const GemvArgs &g, hipStream_t s);
 // lmhead.hip: decode-batch LM head in one launch (9..128 rows; K = 1024, f16 W):
@@ -144,6 +148,8 @@ void launch_gemv(int epi, const GemvArgs &g, hipStream_t s);
 // per-row first-index argmax, and the fused bookkeeping of EPI_ARGMAX above
 // (plus nkv); amax and done zero at rest.  false = shape not covered
 bool launch_lmhead_batch(const GemvArgs &g, hipStream_t s);
+// workgroups of a launch_lmhead_batch launch on the current device (rows of GemvArgs::lp_part)
+int lmhead_grid();
 // gemv.hip: one-row f16 fast path of launch_gemv (false = not covered)
 bool launch_gemv1(int epi, const GemvArgs &g, hipStream_t s);
 
@@ -198,6 +204,9 @@ struct FuseCfg {
                                         // utterance sets over a smaller pool); 0: such an id is rejected as out of range
     int poison = 0;                     // test only: scratch buffers grown by the context are filled with 0xFF bytes
                                         // (fp16 NaN) so a kernel reading rows it never wrote shows up in its outputs
+    int token_logprobs = 0;             // every greedy step also yields the log-probability of its argmax token
+                                        // (qasr_get_*logprobs): in the one-launch LM head where that runs (lmhead.hip
+                                        // LSE), else from the fp32 logits by launch_token_logprob; 0: nothing changes
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
@@ -372,6 +381,12 @@ void launch_embed(const int32_t *ids, int rows, const uint16_t *embd, int hidden
 void launch_argmax_finish(const unsigned long long *amax, int B, int32_t *ids, int32_t *hist, int hist_stride,
                           const int *step, hipStream_t s);
 void launch_fill_u64(unsigned long long *p, int n, unsigned long long v, hipStream_t s);
+// log-probability of each row's chosen token from the fp32 logits [B][ld] the LM
+// head wrote: lp = logits[b][tok[b]] - logsumexp(logits[b][0 .. n_valid)), to
+// lp_out[b] and lp_hist[b][*step] (the slot of the token just written to hist);
+// n_valid = 0: every column
+void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const int32_t *tok, const int *step, float *lp_out,
+                          float *lp_hist, int hist_stride, hipStream_t s);
 // dst row r = src row idx[r], fp32 rows of D floats (D % 4 == 0)
 void launch_gather_rows(const float *src, const int *idx, int rows, int D, float *dst, hipStream_t s);
 // decode-step bookkeeping on device: n_kv[b] += 1, row_pos[b] += 1, step += 1

@@ -22,6 +22,22 @@
 // units, and reduces those once at the end: one atomicMax per row per
 // workgroup, then the last workgroup decodes the tokens (tok, hist[step+1],
 // pos += 1, n_kv += 1, step += 1) and re-arms amax / done (zero at rest).
+//
+// LSE = true (GemvArgs::lp_part set, option token_logprobs) adds the
+// log-probability of each row's argmax to the same launch: beside its best key
+// every lane keeps a running (m, s) of the log-sum-exp over the columns it
+// owns (dev_common.h lse_add), reduced over the 16 column lanes by
+// xor-shuffles and over the waves through LDS in wave order; each workgroup
+// publishes one packed (m, s) per row to lp_part[workgroup][row] with an
+// 8-byte agent-scope atomic store -- past the workgroup's XCD L2, complete
+// before the s_waitcnt vmcnt(0) that precedes its `done` arrival -- and the
+// last workgroup reads them with agent-scope atomic loads (as it reads amax),
+// merges them per row in a fixed order (LPR lanes a row, each over the
+// workgroups w = lane, lane + LPR, ... ascending in rounds of 16, then an
+// xor-shuffle tree)
+// and writes lp_out / lp_hist next to tok_out / hist.  No floating-point
+// atomics: the value does not depend on arrival order.  LSE = false is the
+// kernel as it was.
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -40,10 +56,50 @@ __device__ __forceinline__ int lmh_off(int row, int k) {   // element offset of 
     return row * LMH_K + ((ch ^ (row & 15)) << 3) + (k & 7);
 }
 
-template <int MT, int WPG, int D>
+// last workgroup, every thread: row tid / LPR's (m, s) over the G workgroups' partials, 16 loads in
+// flight a lane; then the log-probability of the row's argmax (the value in its amax key, still
+// armed) to lp_out / lp_hist[row][st + 1]
+template <int LPR>
+__device__ __forceinline__ void lse_finish(const GemvArgs &g, int M, int G, int st) {
+    const int tid = threadIdx.x, row = tid / LPR, sub = tid % LPR;
+    float m = -INFINITY, s = 0.f;
+    if (row < M) {
+        for (int w0 = sub; w0 < G; w0 += 16 * LPR) {
+            unsigned long long p[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const int w = w0 + u * LPR;
+                p[u] = __hip_atomic_load(g.lp_part + (long)(w < G ? w : w0) * 128 + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // the round's pair: its largest m, then 16 independent terms (one dependent merge a round, not 16)
+            float mr = -INFINITY, sr = 0.f;
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (w0 + u * LPR < G) mr = fmaxf(mr, lse_pack_m(p[u]));
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (w0 + u * LPR < G) {
+                    const float mu = lse_pack_m(p[u]), su = lse_pack_s(p[u]);
+                    sr += mu == mr ? su : su * lse_exp(mu - mr);
+                }
+            lse_merge(m, s, mr, sr);
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if (sub == 0 && row < M) {
+        const unsigned long long k = __hip_atomic_load(g.amax + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float lp = lse_logprob(argmax_key_val(k), m, s);
+        g.lp_out[row] = lp;
+        g.lp_hist[(long)row * g.hist_stride + st + 1] = lp;
+    }
+}
+
+template <int MT, int WPG, int D, bool LSE>
 __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];   // [MT*16][LMH_K] fp16, swizzled
     __shared__ unsigned long long bestk[WPG][MT * 16];
+    __shared__ float2 lsek[LSE ? WPG : 1][LSE ? MT * 16 : 1];
     __shared__ int last_wg, st;
     stamp_start(g.stamp);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -115,6 +171,13 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
     for (int i = 0; i < MT; i++)
 #pragma unroll
         for (int r = 0; r < 4; r++) best[i][r] = 0ull;
+    float lm[LSE ? MT : 1][4], ls[LSE ? MT : 1][4];   // LSE: this lane's (m, s) per row over its columns
+    if constexpr (LSE) {
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) { lm[i][r] = -INFINITY; ls[i][r] = 0.f; }
+    }
     floatx4 acc[2][MT];   // even / odd K chunks: the skinny kernel's two K waves (bit-identical logits)
     const int nvalid = g.n_valid > 0 ? g.n_valid : g.N;
     for (int j0 = 0; j0 < n_items; j0 += D) {
@@ -147,6 +210,9 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
                         if (g.out_f32 && row < M) g.out_f32[(long)row * g.ldo + col] = v;
                         const unsigned long long key = col < nvalid ? argmax_key(v, col) : 0ull;
                         best[i][r] = key > best[i][r] ? key : best[i][r];
+                        if constexpr (LSE) {
+                            if (col < nvalid) lse_add(lm[i][r], ls[i][r], v);
+                        }
                     }
             }
         }
@@ -164,6 +230,12 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
                 k = t > k ? t : k;
             }
             if (c16 == 0) bestk[wid][i * 16 + 4 * q + r] = k;
+            if constexpr (LSE) {
+                float m = lm[i][r], s = ls[i][r];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+                if (c16 == 0) lsek[wid][i * 16 + 4 * q + r] = make_float2(m, s);
+            }
         }
     __syncthreads();
     if (tid < M) {
@@ -172,6 +244,12 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
         for (int w = 1; w < WPG; w++) b = bestk[w][tid] > b ? bestk[w][tid] : b;
         const unsigned long long old = atomicMax(g.amax + tid, b);
         asm volatile("" ::"v"(old));   // returned value used: the max has been performed at L2
+        if constexpr (LSE) {   // this workgroup's (m, s) of the row, the waves in order
+            float m = lsek[0][tid].x, s = lsek[0][tid].y;
+#pragma unroll
+            for (int w = 1; w < WPG; w++) lse_merge(m, s, lsek[w][tid].x, lsek[w][tid].y);
+            __hip_atomic_store(g.lp_part + (long)blockIdx.x * 128 + tid, lse_pack(m, s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -180,6 +258,12 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
     if (last_wg) {
         if (tid == 0) st = *g.step;
         __syncthreads();
+        if constexpr (LSE) {
+            constexpr int LPR = MT == 1 ? 32 : MT == 2 ? 16 : 8;   // lanes a row: 64 WPG threads over MT * 16 rows
+            static_assert(LPR * MT * 16 <= 64 * WPG, "a lane group for every row");
+            lse_finish<LPR>(g, M, gridDim.x, st);
+            __syncthreads();   // amax read before it is re-armed below
+        }
         if (tid < M) {
             const unsigned long long k = __hip_atomic_load(g.amax + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int id = argmax_key_idx(k);
@@ -200,8 +284,8 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
 // 8 waves a CU with a 4-deep ring (tools/micro/lmh_bench.hip, MI355X: 16 rows
 // 60.8 us against 68.9 with 16 waves x 3; 64 rows: 6- and 8-deep rings and 4
 // waves x 8 or 12 slower)
-template <int MT, int WPG = 8, int D = 4>
-void run_lmhead(const GemvArgs &g, hipStream_t s) {
+template <int MT, bool LSE, int WPG = 8, int D = 4>
+void run_lmhead_v(const GemvArgs &g, hipStream_t s) {
     static int ncu_dev[64];   // per device: CU count once the LDS attribute is set
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -209,11 +293,16 @@ void run_lmhead(const GemvArgs &g, hipStream_t s) {
     if (!ncu) {
         int n = 0;
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipFuncSetAttribute((const void *)lmhead_batch_kernel<MT, WPG, D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)lmhead_batch_kernel<MT, WPG, D, LSE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   MT * 16 * LMH_K * 2);
         ncu = n > 0 ? n : 256;
     }
-    hipLaunchKernelGGL((lmhead_batch_kernel<MT, WPG, D>), dim3(ncu), dim3(64 * WPG), MT * 16 * LMH_K * 2, s, g);
+    hipLaunchKernelGGL((lmhead_batch_kernel<MT, WPG, D, LSE>), dim3(ncu), dim3(64 * WPG), MT * 16 * LMH_K * 2, s, g);
+}
+template <int MT>
+void run_lmhead(const GemvArgs &g, hipStream_t s) {
+    if (g.lp_part) run_lmhead_v<MT, true>(g, s);
+    else run_lmhead_v<MT, false>(g, s);
 }
 
 // ---- 65..128 rows in one launch, the embedding read once (round 6).  The
@@ -237,6 +326,7 @@ constexpr int L128_R = 4;                  // ring slots (32 KB each)
 constexpr int L128_UNIT = 16 * LMH_K;      // halves per unit
 constexpr int L128_LDS = L128_R * L128_UNIT * 2;
 
+template <bool LSE>
 __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
     extern __shared__ __attribute__((aligned(16))) uint16_t ring[];   // [L128_R][16][LMH_K], swizzled
     __shared__ int last_wg, st;
@@ -313,6 +403,7 @@ __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
 
     // ---- stream: unit j from slot j % R; unit j + R - 1 issued once every wave is past unit j - 1
     unsigned long long best[4] = {0ull, 0ull, 0ull, 0ull};
+    float lm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, ls[4] = {0.f, 0.f, 0.f, 0.f};   // LSE: (m, s) per row
     const int nvalid = g.n_valid > 0 ? g.n_valid : g.N;
     for (int j = 0; j < nu; j++) {
         // this wave's pieces of unit j landed: the units after it still in flight (four pieces each)
@@ -340,6 +431,9 @@ __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
             if (g.out_f32 && row < M) g.out_f32[(long)row * g.ldo + col] = v;
             const unsigned long long key = col < nvalid ? argmax_key(v, col) : 0ull;
             best[r] = key > best[r] ? key : best[r];
+            if constexpr (LSE) {
+                if (col < nvalid) lse_add(lm[r], ls[r], v);
+            }
         }
     }
 
@@ -357,6 +451,13 @@ __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
             const unsigned long long old = atomicMax(g.amax + row, k);
             asm volatile("" ::"v"(old));   // returned value used: the max has been performed at L2
         }
+        if constexpr (LSE) {
+            float m = lm[r], s = ls[r];
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+            if (c16 == 0 && row < M)
+                __hip_atomic_store(g.lp_part + (long)blockIdx.x * 128 + row, lse_pack(m, s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -365,6 +466,10 @@ __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
     if (last_wg) {
         if (tid == 0) st = *g.step;
         __syncthreads();
+        if constexpr (LSE) {
+            lse_finish<4>(g, M, gridDim.x, st);   // 512 threads over 128 rows
+            __syncthreads();   // amax read before it is re-armed below
+        }
         if (tid < M) {
             const unsigned long long k = __hip_atomic_load(g.amax + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int id = argmax_key_idx(k);
@@ -382,6 +487,7 @@ __global__ __launch_bounds__(512) void lmhead128_kernel(GemvArgs g) {
     stamp_end(g.stamp);
 }
 
+template <bool LSE>
 void run_lmhead128(const GemvArgs &g, hipStream_t s) {
     static int ncu_dev[64];
     int dev = 0;
@@ -390,21 +496,30 @@ void run_lmhead128(const GemvArgs &g, hipStream_t s) {
     if (!ncu) {
         int n = 0;
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipFuncSetAttribute((const void *)lmhead128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L128_LDS);
+        (void)hipFuncSetAttribute((const void *)lmhead128_kernel<LSE>, hipFuncAttributeMaxDynamicSharedMemorySize, L128_LDS);
         ncu = n > 0 ? n : 256;
     }
-    hipLaunchKernelGGL(lmhead128_kernel, dim3(ncu), dim3(512), L128_LDS, s, g);
+    hipLaunchKernelGGL(lmhead128_kernel<LSE>, dim3(ncu), dim3(512), L128_LDS, s, g);
 }
 
 }  // namespace
+
+int lmhead_grid() {   // (run_lmhead_v / run_lmhead128: one workgroup a CU, 256 where the query fails)
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+}
 
 bool launch_lmhead_batch(const GemvArgs &g, hipStream_t s) {
     if (g.M < 1 || g.M > 128 || g.K != LMH_K || g.N % 16 != 0 || !g.x || !g.norm_w || !g.amax || !g.done || !g.tok_out ||
         !g.step || !g.pos || g.Wd)
         return false;
+    if ((g.lp_part || g.lp_out || g.lp_hist) && !(g.lp_part && g.lp_out && g.lp_hist && g.hist_stride > 0)) return false;
     if (g.M > 64) {   // 65..128 rows: the rows in registers, the embedding read once (round 6; until then one
                       // launch per 64-row half, each streaming all 311 MB: tools/micro/lmh128_bench)
-        run_lmhead128(g, s);
+        if (g.lp_part) run_lmhead128<true>(g, s);
+        else run_lmhead128<false>(g, s);
         return true;
     }
     const int mt = (g.M + 15) / 16;

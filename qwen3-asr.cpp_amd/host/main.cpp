@@ -32,6 +32,7 @@ struct cli_params {
     int32_t max_tokens = 1024, n_threads = 4, device = 0, batch = 16;
     std::vector<int> devices;   // --devices: shard the files over these GPUs
     bool print_progress = false, print_timing = true, print_tokens = false, profile = false;
+    bool logprobs = false;   // --logprobs: per-token log-probabilities (transcribe_params::token_logprobs)
     bool align_mode = false, transcribe_align_mode = false;
 };
 
@@ -46,6 +47,7 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --progress             Print progress during transcription\n");
     fprintf(stderr, "  --no-timing            Don't print timing information\n");
     fprintf(stderr, "  --tokens               Print token IDs\n");
+    fprintf(stderr, "  --logprobs             Per-token log-probabilities: avg / min per file, and with --tokens each token's\n");
     fprintf(stderr, "  --profile              Print timing profile\n");
     fprintf(stderr, "  --device <n>           HIP device index (default: 0)\n");
     fprintf(stderr, "  --file-list <path>     Text file with one audio path per line (added to the -f files)\n");
@@ -100,6 +102,7 @@ static bool parse(int argc, char **argv, cli_params &p) {
         else if (!strcmp(a, "--progress")) p.print_progress = true;
         else if (!strcmp(a, "--no-timing")) p.print_timing = false;
         else if (!strcmp(a, "--tokens")) p.print_tokens = true;
+        else if (!strcmp(a, "--logprobs")) p.logprobs = true;
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
         else if (!strcmp(a, "-a") || !strcmp(a, "--transcribe-align")) p.transcribe_align_mode = true;
@@ -399,6 +402,7 @@ static int run_transcription(const cli_params &p) {
     tp.n_threads = p.n_threads;
     tp.print_progress = p.print_progress;
     tp.print_timing = p.print_timing;
+    tp.token_logprobs = p.logprobs;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));
@@ -414,12 +418,23 @@ static int run_transcription(const cli_params &p) {
         results = asr.transcribe_batch(clips, tp);
     }
     std::string all;
-    for (const auto &r : results) {
+    for (size_t f = 0; f < results.size(); f++) {
+        const auto &r = results[f];
         if (!r.success) { fprintf(stderr, "Error: %s\n", r.error_msg.c_str()); return 1; }
+        const bool lp = p.logprobs && r.token_logprobs.size() == r.tokens.size();
         if (p.print_tokens) {
             fprintf(stderr, "\nTokens (%zu):\n", r.tokens.size());
-            for (size_t k = 0; k < r.tokens.size(); ++k) fprintf(stderr, "  [%zu] %d\n", k, r.tokens[k]);
+            for (size_t k = 0; k < r.tokens.size(); ++k) {
+                if (lp) fprintf(stderr, "  [%zu] %d %.4f\n", k, r.tokens[k], r.token_logprobs[k]);
+                else fprintf(stderr, "  [%zu] %d\n", k, r.tokens[k]);
+            }
             fprintf(stderr, "\n");
+        }
+        if (lp && !r.tokens.empty()) {
+            double sum = 0.0;
+            float mn = r.token_logprobs[0];
+            for (float v : r.token_logprobs) { sum += v; mn = std::min(mn, v); }
+            fprintf(stderr, "%s: avg_logprob %.4f min_logprob %.4f\n", p.audio_paths[f].c_str(), sum / r.tokens.size(), mn);
         }
         all += r.text + "\n";
     }

@@ -100,6 +100,17 @@ bool Qwen3ASR::ensure_ctx(int batch, int n_ctx) {
     return true;
 }
 
+// context option token_logprobs as the call asks (set only on a change: setting drops the decode graphs)
+bool Qwen3ASR::set_logprobs(bool on) {
+    int cur = 0;
+    if (qasr_ctx_get_option(ctx_, "token_logprobs", &cur) == 0 && (cur != 0) == on) return true;
+    if (qasr_ctx_set_option(ctx_, "token_logprobs", on ? 1 : 0) != 0) {
+        error_msg_ = std::string("Failed to set token_logprobs: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
 transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const transcribe_params &params) {
     transcribe_result result;
     if (!model_) { result.error_msg = "Model not loaded"; return result; }
@@ -144,7 +155,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         sys.resize(std::max(k, 0));
         qasr_tokenize(model_, params.system_prompt.c_str(), sys.data(), k);
     }
-    if (!ensure_ctx(B, maxP + (int)sys.size() + params.max_tokens)) {
+    if (!ensure_ctx(B, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -169,10 +180,20 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         rep.resize(std::max(len, 0));
         profile_report_ = rep;
     }
+    std::vector<float> lps;
+    if (params.token_logprobs) {
+        lps.resize((size_t)B * params.max_tokens);
+        if (qasr_get_logprobs(ctx_, lps.data(), B, params.max_tokens) != 0) {
+            for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+            return out;
+        }
+    }
     const int64_t t1 = now_ms();
     for (int b = 0; b < B; b++) {
         transcribe_result &r = out[b];
         r.tokens.assign(toks.begin() + (long)b * params.max_tokens, toks.begin() + (long)b * params.max_tokens + nt[b]);
+        if (params.token_logprobs)
+            r.token_logprobs.assign(lps.begin() + (long)b * params.max_tokens, lps.begin() + (long)b * params.max_tokens + nt[b]);
         const int len = qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), nullptr, 0);
         std::string text(std::max(len, 0) + 1, '\0');
         qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), &text[0], (int)text.size());
@@ -221,6 +242,7 @@ struct StreamCtx {
     qasr_model *model;
     std::vector<float> pcm;
     int64_t t0;
+    qasr_ctx *lp_ctx;   // non-null: transcribe_params::token_logprobs
 };
 int stream_fetch(void *u, const float **pcm, int *n, int *) {
     StreamCtx *s = (StreamCtx *)u;
@@ -237,6 +259,10 @@ void stream_sink(void *u, int id, int status, const int32_t *toks, int n) {
         r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
     } else {
         r.tokens.assign(toks, toks + n);
+        if (s->lp_ctx) {
+            r.token_logprobs.resize(n);
+            if (qasr_stream_logprobs(s->lp_ctx, r.token_logprobs.data(), n) != n) r.token_logprobs.clear();
+        }
         const int len = qasr_detokenize(s->model, toks, n, nullptr, 0);
         std::string text(std::max(len, 0) + 1, '\0');
         qasr_detokenize(s->model, toks, n, &text[0], (int)text.size());
@@ -263,13 +289,13 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     // chunking unit) plus the budget -- longer clips fail alone ("Context length")
     const int need = n_ctx > 0 ? n_ctx : qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(30 * 16000))) + (int)sys.size() + params.max_tokens;
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
-    if (!ensure_ctx(S, need)) return false;
+    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs)) return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
     const bool per_token = progress_callback_ || params.print_progress;
     qasr_set_token_callback(ctx_, per_token ? stream_token_cb : nullptr, per_token ? &tcb : nullptr);
-    StreamCtx sc{&fetch, &sink, model_, {}, now_ms()};
+    StreamCtx sc{&fetch, &sink, model_, {}, now_ms(), params.token_logprobs ? ctx_ : nullptr};
     const int rc = qasr_run_stream(ctx_, S, stream_fetch, stream_sink, &sc, params.max_tokens, 0, nullptr);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
     if (rc != 0) { error_msg_ = std::string("Decoding failed: ") + qasr_last_error(); return false; }

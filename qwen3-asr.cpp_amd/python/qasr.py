@@ -34,6 +34,7 @@ EXPORTS = [
     "qasr_align", "qasr_align_tokenize", "qasr_model_load_korean_dict", "qasr_fix_timestamps",
     "qasr_align_prompt_len", "qasr_align_json", "qasr_align_json_batch", "qasr_align_words",
     "qasr_ctx_grow_shape",
+    "qasr_get_step_logprobs", "qasr_get_logprobs", "qasr_stream_logprobs",
 ]
 
 
@@ -111,6 +112,8 @@ def lib() -> C.CDLL:
             "qasr_get_probe_device": ([P, C.POINTER(C.c_double), C.POINTER(C.c_int64)], I),
             "qasr_ctx_set_option": ([P, C.c_char_p, I], I), "qasr_ctx_get_option": ([P, C.c_char_p, IP], I),
             "qasr_debug_read": ([P, C.c_char_p, P, C.c_int64], I),
+            "qasr_get_step_logprobs": ([P, F, I], I), "qasr_get_logprobs": ([P, F, I, I], I),
+            "qasr_stream_logprobs": ([P, F, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -286,13 +289,23 @@ class Model:
 class RunResult:
     tokens: List[List[int]]
     timings: Timings
+    # log-probability of every token (context option "token_logprobs"), the shape of tokens; None with the option off
+    logprobs: Optional[List[List[float]]] = None
 
 
-def _sink_into(out: dict, failed: list):
+def _sink_into(out: dict, failed: list, ctx=None):
+    """ctx: the running context when the caller asked for log-probabilities --
+    the sink then stores (tokens, logprobs) per clip (qasr_stream_logprobs)"""
     def sink(_u, cid, status, toks, n):
         try:
             if status:
                 out[cid] = QasrError(lib().qasr_last_error().decode(errors="replace"))
+            elif ctx is not None:
+                lp = np.zeros(max(n, 1), np.float32)
+                k = lib().qasr_stream_logprobs(ctx.h, _f(lp), n)
+                if k != n:
+                    raise QasrError(f"qasr_stream_logprobs: {lib().qasr_last_error().decode(errors='replace')}")
+                out[cid] = ([int(toks[i]) for i in range(n)], lp[:n].tolist())
             else:
                 out[cid] = [int(toks[i]) for i in range(n)]
         except BaseException as e:   # (ctypes would swallow it)
@@ -439,7 +452,22 @@ class Context:
         nt = np.zeros(B, np.int32)
         t = Timings()
         _check(lib().qasr_run(self.h, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)), "qasr_run")
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t)
+        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens))
+
+    def _run_logprobs(self, nt, max_tokens: int):
+        """the last run's log-probabilities per row (None with option token_logprobs off)"""
+        if not self.get_option("token_logprobs"):
+            return None
+        B = len(nt)
+        lp = np.zeros((B, max_tokens), np.float32)
+        _check(lib().qasr_get_logprobs(self.h, _f(lp), B, max_tokens), "qasr_get_logprobs")
+        return [lp[b, :nt[b]].tolist() for b in range(B)]
+
+    def step_logprobs(self, B: int) -> np.ndarray:
+        """log-probability of each row's argmax of the last prefill / decode_step (option token_logprobs)"""
+        out = np.zeros(B, np.float32)
+        _check(lib().qasr_get_step_logprobs(self.h, _f(out), B), "qasr_get_step_logprobs")
+        return out
 
     def run_staged(self, clips: Sequence[int], max_tokens: int, ignore_eos: bool = False) -> RunResult:
         """transcribe staged clips (indices into the last stage_audio call) as one batch"""
@@ -450,14 +478,15 @@ class Context:
         t = Timings()
         _check(lib().qasr_run_staged(self.h, _i(idx), B, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)),
                "qasr_run_staged")
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t)
+        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens))
 
-    def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0):
+    def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0, logprobs: bool = False):
         """Continuous batching (qasr_run_stream): next_clip() -> (id, pcm[, budget])
         or None when the queue is empty; returns ({id: tokens | QasrError},
         StreamStats).  Slots (0: max_batch) freed by a finished clip are
         refilled at the next chunk boundary; a clip that fails alone maps to
-        its QasrError."""
+        its QasrError.  logprobs=True (option token_logprobs on): a clip maps
+        to (tokens, logprobs) instead."""
         out, keep = {}, []
 
         def fetch(_u, pcm_pp, n_p, budget_p):
@@ -473,7 +502,7 @@ class Context:
             return cid
 
         failed = []
-        f, k = FETCH_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed))
+        f, k = FETCH_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None))
         st = StreamStats()
         rc = lib().qasr_run_stream(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
         if failed:
@@ -481,7 +510,8 @@ class Context:
         _check(rc, "qasr_run_stream")
         return out, st
 
-    def run_stream_staged(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0):
+    def run_stream_staged(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0,
+                          logprobs: bool = False):
         """run_stream over the staged pool (stage_audio): next_clip() -> staged
         index (its id) or (index, budget), None when the queue is empty"""
         out = {}
@@ -496,7 +526,7 @@ class Context:
             return int(item)
 
         failed = []
-        f, k = FETCH_STAGED_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed))
+        f, k = FETCH_STAGED_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None))
         st = StreamStats()
         rc = lib().qasr_run_stream_staged(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
         if failed:
