@@ -1,0 +1,293 @@
+// engine_impl.h -- internal to the engine*.hip units (the C-ABI implementation,
+// include/qasr_capi.h): the model and context structs and the helpers the units
+// share.  The host side by unit:
+//   engine.hip         errors, context create / free / options, buffers, counters, profile report
+//   engine_model.hip   GGUF load into the device arena, tokenizer, WAV / synthetic-GGUF utilities
+//   engine_stages.hip  mel, encoder, prefill (run_* and their qasr_* entry points), Q8_0 GEMM helpers
+//   engine_decode.hip  the decode-step emitter, graph capture, kernel probes, qasr_decode_step
+//   engine_run.hip     qasr_run, the continuous-batching stream, their log-probability readers
+//   engine_align.hip   the forced aligner and its JSON output
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/qasr_capi.h"
+#include "../host/gguf.h"
+#include "../host/qasr_host.h"
+#include "dev_common.h"
+#include "kernels.h"
+
+// (hidden visibility: the shared helpers stay out of libqasr.so's dynamic symbols, as when they were static)
+namespace qasr {
+namespace eng __attribute__((visibility("hidden"))) {
+// the calling thread's last error (qasr_last_error): one definition, engine.hip
+int fail(int code, const std::string &msg);
+}  // namespace eng
+}  // namespace qasr
+
+#define HIPCHK(x)                                                                                  \
+    do {                                                                                           \
+        hipError_t e_ = (x);                                                                       \
+        if (e_ != hipSuccess) return ::qasr::eng::fail(QASR_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// ------------------------------------------------------------------ model
+// Linear weights are fp16 [N][K] (F16 files) or int8 [N][K] quants with fp16
+// block scales *_d [N][K/32] (Q8_0 files: block_q8_0 split in two arrays).
+struct EncLayer {
+    uint16_t *wqkv, *wo, *w1, *w2;
+    uint16_t *wqkv_d = nullptr, *wo_d = nullptr, *w1_d = nullptr, *w2_d = nullptr;
+    float *bqkv, *bo, *b1, *b2, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+};
+struct DecLayer {
+    float *attn_norm, *q_norm, *k_norm, *ffn_norm;
+    uint16_t *wqkv, *wo, *wgu, *wd;
+    uint16_t *wqkv_d = nullptr, *wo_d = nullptr, *wgu_d = nullptr, *wd_d = nullptr;
+};
+
+struct qasr_model {
+    qasr::Hparams hp;
+    int device = 0;
+    qasr::Tokenizer tok;
+    char *arena = nullptr;
+    size_t arena_bytes = 0;
+    uint16_t *conv1_w, *conv2_w, *conv3_w, *conv_out_w, *proj1_w, *proj2_w, *embd;
+    uint16_t *conv_out_d = nullptr, *proj1_d = nullptr, *proj2_d = nullptr;
+    bool q8 = false;   // linear weights are Q8_0 (scripts/convert_hf_to_gguf.py:230-308)
+    uint16_t *cls_w = nullptr;   // aligner: classify head [cls_rows][hidden] fp16, rows >= classify_num zero
+    int cls_rows = 0;
+    std::unordered_map<std::string, int> ko_dict;   // aligner: Korean word list (src/forced_aligner.cpp:1543-1562)
+    float *conv1_b, *conv2_b, *conv3_b, *ln_post_w, *ln_post_b, *proj1_b, *proj2_b, *out_norm;
+    std::vector<EncLayer> enc;
+    std::vector<DecLayer> dec;
+    uint16_t *gelu;
+    float *pe, *filters;
+    double2 *tw;
+    double *hann;
+    ~qasr_model() {
+        if (arena && device >= 0) {
+            (void)hipSetDevice(device);
+            (void)hipFree(arena);
+        }
+    }
+};
+
+// --------------------------------------------------------------- context
+// qasr_ctx::ev: the stage boundaries of a run on the context stream
+enum CtxEvent {
+    EV_START,       // before the mel
+    EV_MEL,         // mel | encoder
+    EV_ENC,         // encoder | prefill
+    EV_PREFILL,     // prefill | decode (aligner: after the classify head)
+    EV_END,         // after the last decode step
+    EV_ENC_CONV,    // inside run_encoder, profile only: conv front-end | transformer
+    EV_COUNT
+};
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t n = 0;
+    template <class T> T *as() const { return (T *)p; }
+};
+
+struct qasr_ctx {
+    qasr_model *m = nullptr;
+    int max_batch = 0, max_ctx = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[EV_COUNT] = {};
+    uint16_t *kc = nullptr, *vc = nullptr;
+    uint16_t *vt = nullptr;        // V^T cache (kernels.h vt_ctx): the exact decode attention's V
+    float *rope = nullptr;
+    std::vector<DevBuf> owned;     // everything hipMalloc'ed by the context
+    // grow-on-demand scratch
+    DevBuf pcm, spcm, mel, meltmp, melmax, melclips, melblocks;   // (spcm: qasr_run_stream's host clips)
+    DevBuf chunks, rs1, rs2, rs3, pepos, act1, act2, act3;
+    DevBuf pebig;                  // encode_no_chunk: sinusoidal PE over a whole clip's frames
+    int pebig_rows = 0;
+    DevBuf ex, exh, eqkv, eatt, eff, feats, segs;
+    DevBuf px, pxh, pqkv, pq, patt, pact, prow, plast, pids;
+    DevBuf pq32, pk32;             // ForcedAligner prefill: fp32 Q / K rows
+    DevBuf ats, atx, aam;          // aligner: timestamp-row indices, their normed rows, argmax keys
+    DevBuf exp_, gidx;             // aligner batches: conv_out over every padded chunk row, the valid rows' indices
+    DevBuf q8a, q8d, x32;          // Q8_0 models: quantised activations (int8 + scales), fp32 layer inputs
+    float *d_att32 = nullptr, *d_act32 = nullptr;   // Q8_0 decode: fp32 attention output / SwiGLU output
+    int8_t *d_q8a = nullptr; float *d_q8d = nullptr, *d_x32 = nullptr;   // Q8_0 batched (B > 8) decode, graph-fixed
+    int8_t *d_q8n = nullptr; float *d_q8nd = nullptr;   // ... the RMS-normed layer inputs (QKV, gate/up), quantised
+    // fixed decode state (sized by max_batch)
+    int32_t *d_tok = nullptr, *d_hist = nullptr;
+    int *d_pos = nullptr, *d_nkv = nullptr, *d_slot = nullptr, *d_step = nullptr;
+    float *d_x = nullptr, *d_qkv = nullptr, *d_part = nullptr, *d_logits = nullptr;
+    float *d_scores = nullptr;     // exact decode attention: [B][n_head][max_ctx] scaled scores
+    unsigned int *d_counter = nullptr, *d_done = nullptr;
+    unsigned int *d_qcnt = nullptr;   // fused batch-1 QKV + attention: QKV-block arrivals per kv group
+    unsigned long long *d_gran = nullptr;   // ... or its outputs as tagged granules (zeroed by every prefill)
+    unsigned long long *d_sgran = nullptr;  // ... exact attention: the splits' scores as granules [n_head][max_ctx] (zeroed likewise)
+    bool qkv_in_gran = false;               // the captured step's last layer hands its QKV over in granules
+    unsigned int *d_attdone = nullptr;   // fused batch-1 o-proj: combiner arrivals, [layer][8 replicas][16]
+    unsigned int *d_ffncnt = nullptr;    // fused batch-1 FFN: [layer][gate/up arrivals, o-proj arrivals][32 shards][16]
+    uint16_t *d_att = nullptr, *d_act = nullptr, *d_xh = nullptr;
+    unsigned long long *d_amax = nullptr;
+    int max_splits = 0, hist_cap = 0;
+    // byte sizes of the fixed buffers the host zeroes again after allocating them: the allocation
+    // and every memset take them from here
+    size_t gran_bytes() const { return (size_t)(m->hp.n_head + 2 * m->hp.n_kv_head) * 128 * 8; }
+    size_t sgran_bytes() const { return (size_t)m->hp.n_head * qasr::sgran_ld(max_ctx) * 8; }
+    size_t ffncnt_bytes() const { return (size_t)m->hp.dec_layers * 1024 * 4; }
+    size_t qcnt_bytes() const { return (size_t)m->hp.n_kv_head * 8 * 16 * 4; }
+    size_t attdone_bytes() const { return (size_t)m->hp.dec_layers * 128 * 4; }
+    size_t counter_bytes() const { return (size_t)max_batch * m->hp.n_kv_head * 4; }
+    size_t amax_bytes() const { return (size_t)max_batch * 8; }
+    static constexpr size_t kDoneBytes = 4;
+    // option token_logprobs: the last step's log-probabilities [B], their history parallel to d_hist
+    // (stride hist_cap, the index of the token they belong to), the one-launch LM head's per-workgroup
+    // (m, s) partials [lmhead_grid()][128]
+    float *d_lp = nullptr, *d_lphist = nullptr;
+    unsigned long long *d_lppart = nullptr;
+    int lp_step_B = 0;             // rows of the last qasr_prefill* / qasr_decode_step with the option on (0: none)
+    std::vector<float> lp_run;     // the last qasr_run's values [lp_run_B][lp_run_T], aligned with its tokens
+    std::vector<int> lp_run_n;     // ... and how many per row
+    int lp_run_B = 0, lp_run_T = 0;
+    const std::vector<float> *lp_sink = nullptr;   // inside a qasr_sink_fn call: the delivered clip's values
+    // pinned host staging for small per-call tables (reset at each top-level call)
+    char *pin = nullptr;
+    size_t pin_cap = 0, pin_used = 0;
+    std::vector<int32_t> sys_ids;
+    // staged audio
+    std::vector<int> staged_n;
+    std::vector<long> staged_off;
+    bool eager = false;            // QASR_NO_GRAPH=1: launch the decode step eagerly (profilers)
+    int dev_skip = 0;              // QASR_DEV_SKIP bitmask (-DQASR_DIAG_SKIP builds only): omits decode kernels
+    qasr::FuseCfg fuse;                 // batch-1 fused launches: switches, delays, co-residency of this device
+    unsigned int *d_err = nullptr; // sticky device error word of the fused launches (DevErr bits)
+    int dbg_layers = 0;            // diagnostic: decode steps run only the first n decoder layers (0 = all)
+    // --profile (src/timing.h QWEN3_TIMER sections): per-section device time from
+    // HIP events, accumulated over calls until qasr_set_profile resets it
+    bool profile_on = false;
+    std::map<std::string, std::pair<double, long>> prof;   // section -> (total ms, calls)
+    std::vector<hipEvent_t> step_ev;                       // per decode step, profile only
+    // per-token callback (src/qwen3_asr.cpp:264-291): called synchronously
+    // after every greedy step of qasr_run, in order, for every live sequence
+    void (*tok_cb)(void *user, int seq, int n_generated, int32_t token) = nullptr;
+    void *tok_cb_user = nullptr;
+    // QASR_DEV_TRACE=<file>: per-block timestamps of one decode layer's kernels
+    // (layer QASR_DEV_TRACE_LAYER, default 10) of the last step, dumped by qasr_run
+    std::string trace_path;
+    int trace_layer = 10;
+    unsigned long long *d_trace = nullptr;   // [6 kernels][4096 blocks][8]
+    static constexpr size_t kTraceBytes = (size_t)6 * 4096 * 8 * 8;
+    // kernel probe: HIP-event timing of one decode-step kernel inside qasr_run
+    int probe = 0;                 // 0 off, 1 LM head, 2 layer QKV + attention, 3 layer FFN
+    int probe_layer = 14;          // decoder layer whose groups probes 2 / 3 time
+    int probe_stride = 1;          // probe decode steps k with k % probe_stride == 0 (the others replay the whole-step
+                                   // graph: the probed step's split graphs and eager group cost ~3 % of a step)
+    bool probe_o_fused = false;    // the probed layer's o-projection runs inside the QKV launch
+    int last_fmode = 0, last_fx = 0;   // the last emitted decode step, layer 0: fused launch mode (0 separate, 1 QKV +
+                                       // attention, 2 + o-proj) and whether its attention was the chain role (options
+                                       // "fused_mode" / "fused_exact", read-only)
+    int last_attn = 0;             // the same step's decode attention launches (option "attn_path", read-only): 0 split-K
+                                   // fp32, 1 chain role of the fused launch, 2 scores + chain in one launch per sequence
+                                   // (decode_attn_seq_kernel), 3 separate scores and chain kernels
+    double probe_ms = 0.0, probe_bytes = 0.0, probe_dev_ms = 0.0;
+    long probe_dev_n = 0;
+    unsigned long long *d_pstamp = nullptr;   // per decode step: [32 min-starts | 32 max-ends] of the probed launches
+    unsigned long long *cur_stamp = nullptr;  // record of the group being emitted (probe only)
+    long probe_n = 0;
+    std::vector<int> run_P;        // prompt lengths of the current qasr_run (decode step k: n_kv = P_b + k + 1)
+    std::vector<hipEvent_t> pev;
+    // decode graphs, one set per attention split-grid bucket (the grid must
+    // cover the longest sequence's context: it grows by 64 keys per split)
+    struct StepGraphs { hipGraphExec_t full = nullptr, pre = nullptr, post = nullptr; };
+    std::map<int, StepGraphs> graphs;   // key: batch * 65536 + split bucket
+    int graph_B = -1;
+    bool graph_logits = false;
+    int graph_base = 0;            // max prompt length of the current run: step k feeds position base + k
+    int graph_probe_group = -1;    // launch group timed between events (pre/post graphs split around it)
+    void drop_graphs() {
+        for (auto &kv : graphs) {
+            if (kv.second.full) (void)hipGraphExecDestroy(kv.second.full);
+            if (kv.second.pre) (void)hipGraphExecDestroy(kv.second.pre);
+            if (kv.second.post) (void)hipGraphExecDestroy(kv.second.post);
+        }
+        graphs.clear();
+    }
+    ~qasr_ctx() {
+        (void)hipSetDevice(m->device);
+        drop_graphs();
+        for (auto &e : pev) (void)hipEventDestroy(e);
+        for (auto &e : step_ev) (void)hipEventDestroy(e);
+        for (auto &b : owned) (void)hipFree(b.p);
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        if (pin) (void)hipHostFree(pin);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+// ------------------------------------------------ helpers the units share
+namespace qasr {
+namespace eng __attribute__((visibility("hidden"))) {
+constexpr int kStampRec = 2 * STAMP_ENDS;   // u64 per probed launch record (dev_common.h stamp_start/end)
+
+// engine.hip
+int declined_check(const char *stage);
+int reset_counters(qasr_ctx *c);
+int reset_granules(qasr_ctx *c);
+int check_dev_err(qasr_ctx *c);
+std::mutex &device_lock(int device);
+int ensure(qasr_ctx *c, DevBuf &b, size_t bytes);
+int stage_pinned(qasr_ctx *c, const void *src, size_t bytes, void *dst);
+
+// V^T cache elements of one layer
+inline size_t layer_vt(const qasr_ctx *c) {
+    return (size_t)c->max_batch * c->m->hp.n_kv_head * 128 * vt_ctx(c->max_ctx);
+}
+inline bool takes_fused(const qasr_ctx *c, int B) {
+    return B == 1 && !c->m->q8 && (c->fuse.ffn || c->fuse.qkv);
+}
+// Small per-call tables go through a pinned staging area so the async copy
+// never reads a host vector that has gone out of scope.
+template <class T>
+int upload(qasr_ctx *c, DevBuf &b, const std::vector<T> &v) {
+    const size_t bytes = v.size() * sizeof(T);
+    const int rc = ensure(c, b, bytes);
+    if (rc || !bytes) return rc;
+    return stage_pinned(c, v.data(), bytes, b.p);
+}
+
+// engine_stages.hip
+void launch_gemm_c(qasr_ctx *c, int amode, int epi, GemmArgs g, hipStream_t s);
+void gemm_q8(qasr_ctx *c, int epi, GemmArgs g, const float *a32, const uint16_t *a16, int lda, int gather_C, const uint16_t *W,
+             const uint16_t *Wd, hipStream_t s, int8_t *qa = nullptr, float *qd = nullptr, bool decode = false);
+void gemm_q8_pre(qasr_ctx *c, int epi, GemmArgs g, const uint16_t *W, const uint16_t *Wd, hipStream_t s,
+                 const int8_t *qa = nullptr, const float *qd = nullptr);
+bool gemm_q8_pre_swiglu_q8(qasr_ctx *c, GemmArgs g, const uint16_t *W, const uint16_t *Wd, hipStream_t s, const int8_t *qa,
+                           const float *qd, int8_t *q, float *d);
+int pack_pcm(qasr_ctx *c, const float *const *pcm, const int *n, int B, std::vector<long> &off);
+int run_mel(qasr_ctx *c, const std::vector<long> &off, const std::vector<int> &n, std::vector<long> &mel_off, std::vector<int> &T,
+            const float *d_pcm = nullptr);
+int run_encoder(qasr_ctx *c, const float *d_mel, const std::vector<long> &mel_off, const std::vector<int> &T, bool conv_only,
+                std::vector<int> &Nb, bool no_chunk = false);
+int prefill_layers(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vector<int> &P, const float *d_feats,
+                   const std::vector<int> &audio_pos, const std::vector<int> &N, const std::vector<int> *slots,
+                   const std::vector<int> *pos0 = nullptr);
+int run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vector<int> &P, const float *d_feats,
+                const std::vector<int> &audio_pos, const std::vector<int> &N, bool want_logits,
+                const std::vector<int> *slots = nullptr, const std::vector<int> *pos0 = nullptr);
+
+// engine_decode.hip
+int split_bucket(qasr_ctx *c, int pos);
+int decode_graph(qasr_ctx *c, int B, bool want_logits, int base);
+int launch_whole_step(qasr_ctx *c, int B, int splits);
+int launch_step(qasr_ctx *c, int B, int k);
+int probe_arm(qasr_ctx *c, int nsteps);
+int probe_collect(qasr_ctx *c, int B, int nsteps);
+}  // namespace eng
+}  // namespace qasr
