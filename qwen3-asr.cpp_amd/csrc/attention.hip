@@ -1560,14 +1560,38 @@ __device__ __forceinline__ void fx1_chain_body(const DecodeAttnArgs &a, const in
         u32x4 va[DX_Q / 8], vb[DX_Q / 8];
         floatx4 wa, wb;
         const int lastb = nl > 0 ? (nl - 1) >> 3 : 0;
+        // buffers 0 .. nfull - 1 lie wholly at or below lastb: the main loop
+        // requests those (the two after the one it starts on) unclamped
+        // (fx_loadQ_sb: 16 KiB a buffer in the scalar offset), two buffers an
+        // iteration; the tail -- the clamped loop, at most three buffers --
+        // runs the rest, so the loads issued and the blocks they read are
+        // those of one clamped loop.  A wave alone on its SIMD pays ~4 cycles
+        // of issue per instruction of any kind: an all-fast buffer of the
+        // main loop is the 128 chain instructions + 45 others, of the tail
+        // 128 + ~90 (tools/chain_loop_count.py)
+        const int nfull = nl > 0 ? (lastb + 1) >> 3 : 0;
+        constexpr uint32_t QB = DX_Q / 8 * 2048;   // bytes between two buffers' key blocks
+        // (the wave's bytes of V^T: 1 KiB of each 2 KiB key block, up to block lastb's)
+        const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void *)vt, (short)0, lastb * 2048 + 1024, 0x00020000);
+        const uint32_t voff = 16 * lane;
+        int jt = 0;
         fx_loadQ(va, vt, loff, 0, lastb);
         fx_w8(fsc[hh], 0, wa, wb);
-        for (int j0 = 0; j0 < nl; j0 += 2 * DX_Q) {
+        // which buffers hold a new maximum, one bit each (kmask is complete:
+        // two barriers since its stores); shifted down two bits an iteration
+        uint32_t bm = fx_buffer_bits(kmask[hh]);
+        for (; jt + 2 * DX_Q < nfull * DX_Q; jt += 2 * DX_Q, bm >>= 2) {
+            fx_loadQ_sb(vb, vrs, voff, (jt / DX_Q + 1) * QB);
+            fx_step1_lds_b(va, jt, fsc[hh], kmask[hh], bm & 1u, acc, wa, wb);
+            fx_loadQ_sb(va, vrs, voff, (jt / DX_Q + 2) * QB);
+            fx_step1_lds_b(vb, jt + DX_Q, fsc[hh], kmask[hh], bm & 2u, acc, wa, wb);
+        }
+        for (int j0 = jt; j0 < nl; j0 += 2 * DX_Q, bm >>= 2) {
             fx_loadQ(vb, vt, loff, j0 + DX_Q, lastb);
-            fx_step1_lds_m(va, j0, fsc[hh], fx_mask64(kmask[hh], j0), acc, wa, wb);
+            fx_step1_lds_b(va, j0, fsc[hh], kmask[hh], bm & 1u, acc, wa, wb);
             if (j0 + DX_Q >= nl) break;
             fx_loadQ(va, vt, loff, j0 + 2 * DX_Q, lastb);
-            fx_step1_lds_m(vb, j0 + DX_Q, fsc[hh], fx_mask64(kmask[hh], j0 + DX_Q), acc, wa, wb);
+            fx_step1_lds_b(vb, j0 + DX_Q, fsc[hh], kmask[hh], bm & 2u, acc, wa, wb);
         }
         acc = fx_key_slow(acc, vnew, fwl[hh]);
     }

@@ -239,6 +239,74 @@ __device__ __forceinline__ unsigned long long fx_mask64(const uint16_t *km, int 
            (uint32_t)__builtin_amdgcn_readfirstlane((int)m.x);
 }
 
+// fx_step1_lds_m with the decision "does this buffer hold a new maximum" made
+// by the caller (hit: uniform, one bit of a per-chain bitmap built once before
+// the loop): a buffer without one costs a scalar bit test and a branch, and
+// only a buffer with one reads its 64 mask bits from LDS (km, fx_mask64) for
+// the per-group path -- ~4 of 22 buffers of a 1.37k-key chain.  The per-buffer
+// LDS read of the mask (address add, ds_read_b64, wait, two v_readfirstlane,
+// or, compare) was ~10 of the ~89 non-chain instructions a buffer, each ~4
+// cycles of issue for a wave alone on its SIMD.  Two ifs, the second on a copy
+// of hit the optimiser cannot see through (an empty asm statement): as one
+// if / else the out-of-line branch came back through a flag (s_mov_b64 -1,
+// s_and_b64, s_cbranch_vccz before the fast block) and the accumulator
+// through a copy (s_nop 0, v_mov_b32 after it) in every buffer; this way the
+// fast path is test, branch, test, branch, block.
+__device__ __forceinline__ void fx_step1_lds_b(const u32x4 *v, int j0, const float *ws, const uint16_t *km, bool hit, f16 &acc,
+                                               floatx4 &wa, floatx4 &wb) {
+    uint32_t fast = !hit;
+    asm volatile("" : "+s"(fast));
+    if (__builtin_expect(hit, 0)) {   // out of line
+        const unsigned long long m64 = fx_mask64(km, j0);
+#pragma unroll
+        for (int g8 = 0; g8 < DX_Q / 8; g8++) {
+            floatx4 na, nb;
+            fx_w8(ws, j0 + 8 * g8 + 8, na, nb);
+            if (((m64 >> (8 * g8)) & 0xffull) != 0) fx8_slow(acc, v[g8], wa, wb);
+            else fx8_fast(acc, v[g8], wa, wb);
+            wa = na;
+            wb = nb;
+        }
+    }
+    if (__builtin_expect(fast != 0u, 1)) {
+#pragma unroll
+        for (int g8 = 0; g8 < DX_Q / 8; g8++) {
+            floatx4 na, nb;
+            fx_w8(ws, j0 + 8 * g8 + 8, na, nb);
+            fx8_fast(acc, v[g8], wa, wb);
+            wa = na;
+            wb = nb;
+        }
+    }
+}
+// bit b = keys 64 b .. 64 b + 63 hold a new maximum (km: the head's DX_KC / 16
+// u16 masks, complete; uniform result): lane b reads buffer b's four masks
+__device__ __forceinline__ uint32_t fx_buffer_bits(const uint16_t *km) {
+    static_assert(DX_KC / DX_Q == 32, "one bit a buffer in 32 bits");
+    const uint2 m = *(const uint2 *)(km + 4 * (threadIdx.x & 31));
+    return (uint32_t)__ballot((m.x | m.y) != 0u);   // (lanes 32 .. 63 repeat 0 .. 31: the upper half is dropped)
+}
+
+// DX_Q keys of V for a buffer that lies wholly at or below the sequence's last
+// key block: no clamp, and the address in a scalar-base form -- buffer loads
+// through a descriptor of the wave's V^T bytes (rs: base = its key block 0,
+// records = up to the end of its last key block, so a load past it would
+// return zeros instead of reading on), the lane's byte offset within the
+// buffer's 16 KiB in a 32-bit VGPR (voff = 16 lane, + 2048 a key block: loop
+// invariants), the buffer in the scalar offset: sb = its first key block
+// times 2048, at most one 32-bit scalar add a buffer.  fx_loadQ's addresses were 24 SALU and 8 64-bit VALU instructions a
+// buffer, the VGPR pairs written just before the loads (s_nop) into registers
+// still awaited as load destinations (vmcnt waits).  The same bytes as
+// fx_loadQ reads for such a buffer; the compiler counts these loads in its
+// s_waitcnt like any other.  (global_load's SGPR-pair form from C++ -- uniform
+// pointer + zero-extended lane offset + constant -- came out as 64-bit VGPR
+// pointers again: hoisted base + offset, v_add_co / v_addc pairs per 4 KiB.)
+__device__ __forceinline__ void fx_loadQ_sb(u32x4 *v, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t sb) {
+#pragma unroll
+    for (int i = 0; i < DX_Q / 8; i++)
+        v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + i * 2048, sb, 0));
+}
+
 // DX_Q keys of V from key block j0 / 8 (vt: the wave's key block 0, uniform;
 // loff = 8 lane: kernels.h vt_index, 1024 halves per block).  Blocks past
 // lastb (the sequence's last key block, uniform) re-read block lastb: the
