@@ -40,6 +40,9 @@
  *       no reference counterpart: sample_greedy keeps the token id and drops
  *       the logits; these return log softmax(logits)[argmax] of every greedy
  *       token (context option "token_logprobs")
+ *   qasr_get_step_topk, qasr_get_topk, qasr_stream_topk
+ *       no reference counterpart: the K largest logits of every greedy step
+ *       as (id, log-probability) pairs (context option "top_k")
  *
  * Conventions (mirroring the reference's):
  *   - return value: 0 = OK, nonzero = error; message via qasr_last_error().
@@ -284,6 +287,41 @@ int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64_t bytes);
 int qasr_get_step_logprobs(qasr_ctx *c, float *out, int B);
 int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens);
 int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap);
+
+/* ---- top-K token alternatives (no reference counterpart) ------------------- */
+/* Context option "top_k" [QASR_TOP_K], 0 .. QASR_TOPK_MAX, default 0 (a value
+ * outside the range is QASR_ERR_ARG): with K > 0 every greedy step also yields,
+ * per row, the K largest logits of the vocabulary row as (id, logprob) pairs in
+ * descending order of the fp32 logit, equal logits by lower id first -- entry 0
+ * is the greedy token -- with logprob = logit - logsumexp(row), the value
+ * "token_logprobs" reports for entry 0 (bit-identical with both options on).
+ * The selection runs on the device -- a small launch over the step's fp32
+ * logits, which the step then writes, or inside the one-launch LM head of
+ * decode batches -- and nothing is copied to the host but the pairs.  Tokens are
+ * the same with the option on or off; it is independent of "token_logprobs".
+ * Setting it invalidates earlier results.  Aligner models ignore it.  (The order
+ * is that of the greedy argmax key, which compares the fp32 bits: -0.0 sorts
+ * below +0.0, where a sort by value would call them equal.)  "lmh_topk"
+ * [QASR_LMH_TOPK] is a diagnostic switch between the two device paths at decode
+ * batches of 9..64 rows (0 / 2: never / always inside the LM head; default 1:
+ * the faster one for this K); results do not depend on it beyond rounding.
+ * K must equal the option's value (else QASR_ERR_ARG).  With the option off, or
+ * before a call of the kind named has run with it on, the three calls return
+ * QASR_ERR_STATE; a null or short buffer is QASR_ERR_ARG.
+ *   qasr_get_step_topk: the last qasr_prefill* / qasr_decode_step; ids and
+ *       logprobs [B][K] row-major (B >= that call's B; that call's rows written)
+ *   qasr_get_topk: the last qasr_run / qasr_run_staged / qasr_transcribe_batch;
+ *       ids and logprobs [B][max_tokens][K], row b's first n_tokens[b] steps
+ *       aligned with its returned tokens (a popped trailing EOS drops its
+ *       alternatives too); B and max_tokens at least the run's batch and
+ *       longest row
+ *   qasr_stream_topk: only inside a qasr_sink_fn call of qasr_run_stream* with
+ *       status 0: the alternatives of the clip being delivered, [n][K] for its n
+ *       tokens (cap_tokens >= n); returns n (>= 0), or minus an error code */
+#define QASR_TOPK_MAX 8
+int qasr_get_step_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int K);
+int qasr_get_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int max_tokens, int K);
+int qasr_stream_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int cap_tokens, int K);
 
 /* Per-token callback (Qwen3ASR::set_progress_callback, src/qwen3_asr.cpp:255-291):
  * called synchronously on the caller's thread after every greedy token of

@@ -29,6 +29,9 @@ struct transcribe_params {
     // MI355X addition (trailing, default off): also return every token's log-probability
     // (context option "token_logprobs" of qasr_capi.h; no reference counterpart)
     bool token_logprobs = false;
+    // MI355X addition (trailing, default off): also return every token's top_k (1..8) alternatives
+    // (context option "top_k" of qasr_capi.h; no reference counterpart)
+    int32_t top_k = 0;
 };
 
 // src/qwen3_asr.h:37-49
@@ -45,6 +48,11 @@ struct transcribe_result {
     // MI355X addition (trailing): with transcribe_params::token_logprobs, log softmax(logits)[token]
     // of every entry of tokens (same length); empty otherwise
     std::vector<float> token_logprobs;
+    // MI355X addition (trailing): with transcribe_params::top_k = K > 0, the K largest logits of every
+    // token's step as ids and log-probabilities, flat [tokens.size()][K] (entry 0 of a step is the
+    // token itself); empty otherwise
+    std::vector<int32_t> alt_tokens;
+    std::vector<float> alt_logprobs;
 };
 
 using progress_callback_t = std::function<void(int tokens_generated, int max_tokens)>;
@@ -88,11 +96,14 @@ public:
     int max_batch() const { return max_batch_; }
     void set_profile(bool on) { profile_ = on; }
     const std::string &profile_report() const { return profile_report_; }
+    // the text of one token id (empty without a model): for listing transcribe_result::alt_tokens
+    std::string token_text(int32_t id) const;
 
 private:
     transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params);
     bool ensure_ctx(int batch, int n_ctx);
     bool set_logprobs(bool on);
+    bool set_top_k(int k);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

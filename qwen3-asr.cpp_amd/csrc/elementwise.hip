@@ -284,6 +284,157 @@ void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const
                        tok, step, lp_out, lp_hist, hist_stride);
 }
 
+// ------------------------------------------------------- top-K alternatives
+// One workgroup a row, two passes over it.  Pass 1 is token_logprob_kernel's:
+// the columns split over the threads in its way and the row's (m, s) folded and
+// merged in its order, so entry 0's log-probability has that kernel's bits;
+// beside its pair every thread keeps the largest argmax key of its columns (a
+// key orders by value, then by lower column: the keys of a row are distinct).
+// The K-th largest of the 1024 thread keys -- K rounds of xor-shuffle max per
+// wave, the lane that held the winner dropping out, then ranks among the 16
+// waves' K keys in LDS -- is a lower bound T of the row's K-th largest key: K
+// distinct keys are at or above it.  Pass 2 reads the row again (L2) and
+// collects the keys >= T in LDS.  They all belong to the K threads whose own
+// largest key is >= T, so there are at most K * (columns a thread) of them
+// (TOPK_CAND holds that; the launcher declines a row too long for it), and
+// nearly always K.  A collected key's rank is the number of collected keys above
+// it: ranks 0 .. K-1 are the row's result, whatever order the LDS atomics
+// appended them in.  Comparisons only: the result depends on the row's logits alone.
+// (Per-thread sorted K-lists merged through LDS, the first form of this
+// kernel, took 97 us a row at K = 8 against 28 at K = 1: some lane of a wave
+// inserts at nearly every column, so every wave ran the insertion for all of
+// its columns -- profiles/topk/topk_cost_thread_lists.txt.)
+constexpr int TOPK_CAND = 2048;
+constexpr int TOPK_INF = 8;
+__global__ __launch_bounds__(1024) void topk_rows_kernel(const float *__restrict__ logits, int ld, int n_valid, int K,
+                                                          const int *__restrict__ step, int32_t *__restrict__ tk_ids,
+                                                          float *__restrict__ tk_lp, int32_t *__restrict__ tk_hist_ids,
+                                                          float *__restrict__ tk_hist_lp, int hist_stride) {
+    __shared__ float wm[16], ws[16];
+    __shared__ unsigned long long wk[16 * TOPK_MAX], cand[TOPK_CAND], tkey;
+    __shared__ int ncand;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float *row = logits + (long)b * ld;
+    if (tid == 0) { tkey = 1ull; ncand = 0; }   // (fewer than K threads with a column: every key passes)
+    float m = -INFINITY, s = 0.f;
+    unsigned long long mk = 0ull;
+    auto take = [&](float v, int col) {
+        lse_add(m, s, v);
+        const unsigned long long k = argmax_key(v, col);
+        mk = k > mk ? k : mk;
+    };
+    const int n4 = (ld & 3) ? 0 : n_valid >> 2;   // float4 columns (rows 16-B aligned), then the tail
+    // (TOPK_INF loads in flight a thread, consumed in column order: one load at a time left a pass waiting
+    // on memory latency, a workgroup being alone on its row)
+    for (int i0 = tid; i0 < n4; i0 += 1024 * TOPK_INF) {
+        float4 v[TOPK_INF];
+#pragma unroll
+        for (int u = 0; u < TOPK_INF; u++) {
+            const int i = i0 + 1024 * u;
+            v[u] = i < n4 ? *(const float4 *)(row + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < TOPK_INF; u++) {
+            const int i = i0 + 1024 * u;
+            if (i < n4) {
+                take(v[u].x, 4 * i);
+                take(v[u].y, 4 * i + 1);
+                take(v[u].z, 4 * i + 2);
+                take(v[u].w, 4 * i + 3);
+            }
+        }
+    }
+    for (int i = 4 * n4 + tid; i < n_valid; i += 1024) take(row[i], i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if (lane == 0) { wm[wid] = m; ws[wid] = s; }
+    for (int j = 0; j < K; j++) {   // the wave's K largest thread keys
+        unsigned long long mx = mk;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(mx, o, 64);
+            mx = t > mx ? t : mx;
+        }
+        if (lane == 0) wk[wid * K + j] = mx;
+        if (mk == mx) mk = 0ull;
+    }
+    __syncthreads();
+    if (tid < 16 * K) {   // T: the key K-1 keys are above
+        const unsigned long long k = wk[tid];
+        int rank = 0;
+        for (int i = 0; i < 16 * K; i++) rank += wk[i] > k;
+        if (k != 0ull && rank == K - 1) tkey = k;
+    }
+    __syncthreads();
+    const unsigned long long T = tkey;
+    auto collect = [&](float v, int col) {
+        const unsigned long long k = argmax_key(v, col);
+        if (k >= T) {
+            const int i = atomicAdd(&ncand, 1);
+            if (i < TOPK_CAND) cand[i] = k;
+        }
+    };
+    for (int i0 = tid; i0 < n4; i0 += 1024 * TOPK_INF) {
+        float4 v[TOPK_INF];
+#pragma unroll
+        for (int u = 0; u < TOPK_INF; u++) {
+            const int i = i0 + 1024 * u;
+            v[u] = i < n4 ? *(const float4 *)(row + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < TOPK_INF; u++) {
+            const int i = i0 + 1024 * u;
+            if (i < n4) {
+                collect(v[u].x, 4 * i);
+                collect(v[u].y, 4 * i + 1);
+                collect(v[u].z, 4 * i + 2);
+                collect(v[u].w, 4 * i + 3);
+            }
+        }
+    }
+    for (int i = 4 * n4 + tid; i < n_valid; i += 1024) collect(row[i], i);
+    __syncthreads();
+    const int n = min(ncand, TOPK_CAND);
+    for (int c = tid; c < max(n, K); c += 1024) {
+        int slot = -1, id = -1;
+        float lp = -INFINITY;
+        if (c < n) {
+            const unsigned long long k = cand[c];
+            int rank = 0;
+            for (int i = 0; i < n; i++) rank += cand[i] > k;
+            if (rank < K) {
+                m = wm[0]; s = ws[0];
+                for (int w = 1; w < 16; w++) lse_merge(m, s, wm[w], ws[w]);
+                slot = rank;
+                id = argmax_key_idx(k);
+                lp = lse_logprob(argmax_key_val(k), m, s);
+            }
+        }
+        if (c >= n && c < K) slot = c;   // fewer than K valid columns: id -1, -inf
+        if (slot >= 0) {
+            tk_ids[(long)b * K + slot] = id;
+            tk_lp[(long)b * K + slot] = lp;
+            if (tk_hist_ids) {
+                const long h = ((long)b * hist_stride + *step) * K + slot;
+                tk_hist_ids[h] = id;
+                tk_hist_lp[h] = lp;
+            }
+        }
+    }
+}
+
+bool launch_topk_rows(const float *logits, int ld, int B, int n_valid, int K, const int *step, int32_t *tk_ids, float *tk_lp,
+                      int32_t *tk_hist_ids, float *tk_hist_lp, int hist_stride, hipStream_t s) {
+    if (K < 1 || K > TOPK_MAX || !logits || !tk_ids || !tk_lp || !step || (tk_hist_ids != nullptr) != (tk_hist_lp != nullptr))
+        return false;
+    const int nv = n_valid > 0 && n_valid < ld ? n_valid : ld;
+    if ((long)K * (nv / 1024 + 8) > TOPK_CAND) return false;   // keys >= T: at most K threads' columns (4 a float4 round + tail)
+    if (B <= 0) return true;
+    hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(1024), 0, s, logits, ld, nv, K, step, tk_ids, tk_lp, tk_hist_ids, tk_hist_lp,
+                       hist_stride);
+    return true;
+}
+
 // dst row r = src row idx[r] (fp32 rows of D floats, 16-B lanes)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, const int *__restrict__ idx, int rows, int D,
                                                           float *__restrict__ dst) {

@@ -62,6 +62,8 @@ static const std::vector<FuseOption> &fuse_options() {
         {"staged_wrap", "QASR_STAGED_WRAP", &FuseCfg::staged_wrap},
         {"poison_scratch", "QASR_POISON_SCRATCH", &FuseCfg::poison},
         {"token_logprobs", "QASR_TOKEN_LOGPROBS", &FuseCfg::token_logprobs},
+        {"top_k", "QASR_TOP_K", &FuseCfg::top_k},
+        {"lmh_topk", "QASR_LMH_TOPK", &FuseCfg::lmh_topk},
     };
     return v;
 }
@@ -142,6 +144,32 @@ int qasr::eng::ensure(qasr_ctx *c, DevBuf &b, size_t bytes) {
     b.n = n;
     c->owned.push_back({b.p, n});
     if (c->fuse.poison) HIPCHK(hipMemsetAsync(b.p, 0xFF, n, c->st));
+    return 0;
+}
+
+// option top_k: its device buffers, sized for QASR_TOPK_MAX, the first time the option is non-zero
+static_assert(QASR_TOPK_MAX == qasr::TOPK_MAX, "the C-ABI's largest K is the row kernel's");
+static int ensure_topk(qasr_ctx *c) {
+    if (c->d_tkpart) return 0;   // (the last of the five: set only once all are)
+    const size_t step = (size_t)c->max_batch * QASR_TOPK_MAX * 4, hist = step * c->hist_cap;
+    int32_t *id = nullptr, *hid = nullptr;
+    float *lp = nullptr, *hlp = nullptr;
+    unsigned long long *part = nullptr;
+    int rc;
+    if ((rc = dev_alloc(c, (void **)&id, step)) || (rc = dev_alloc(c, (void **)&lp, step)) ||
+        (rc = dev_alloc(c, (void **)&hid, hist)) || (rc = dev_alloc(c, (void **)&hlp, hist)) ||
+        (rc = dev_alloc(c, (void **)&part, (size_t)lmhead_grid() * 128 * QASR_TOPK_MAX * 8)))
+        return rc;   // (what was allocated stays owned by the context and is freed with it)
+    c->d_tkid = id; c->d_tklp = lp; c->d_tkhid = hid; c->d_tkhlp = hlp; c->d_tkpart = part;
+    return 0;
+}
+
+int qasr::eng::topk_step(qasr_ctx *c, int B) {
+    const int K = c->fuse.top_k;
+    if (K <= 0) return 0;
+    if (!launch_topk_rows(c->d_logits, c->m->hp.vocab, B, 0, K, c->d_step, c->d_tkid, c->d_tklp, c->d_tkhid, c->d_tkhlp,
+                          c->hist_cap, c->st))
+        return fail(QASR_ERR_STATE, "option top_k: the row kernel declined K = " + std::to_string(K));
     return 0;
 }
 
@@ -226,6 +254,7 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
     for (const auto &o : fuse_options()) {
         if (const char *e = getenv(o.env)) c->fuse.*(o.field) = atoi(e);
     }
+    if (c->fuse.top_k < 0 || c->fuse.top_k > QASR_TOPK_MAX) return fail(QASR_ERR_ARG, "QASR_TOP_K out of range (0..8)");
     fused_slots(c->fuse);   // co-residency on this context's device
     if (const char *tp = getenv("QASR_DEV_TRACE")) {
         c->trace_path = tp;
@@ -270,6 +299,7 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
         (rc = dev_alloc(c.get(), (void **)&c->d_lphist, (size_t)B * max_ctx * 4)) ||
         (rc = dev_alloc(c.get(), (void **)&c->d_lppart, (size_t)lmhead_grid() * 128 * 8)))
         return rc;
+    if (c->fuse.top_k && (rc = ensure_topk(c.get()))) return rc;
     std::vector<int> slots(B);
     for (int b = 0; b < B; b++) slots[b] = b;
     HIPCHK(hipMemcpy(c->d_slot, slots.data(), B * 4, hipMemcpyHostToDevice));
@@ -310,12 +340,23 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
     for (const auto &o : fuse_options())
         if (n == o.name) {
             if (n == "poll_limit" && value <= 0) return fail(QASR_ERR_ARG, "poll_limit must be positive");
+            if (n == "top_k" && (value < 0 || value > QASR_TOPK_MAX)) return fail(QASR_ERR_ARG, "top_k out of range (0..8)");
+            if (n == "top_k" && value > 0) {
+                HIPCHK(hipSetDevice(c->m->device));
+                if (const int rc = ensure_topk(c)) return rc;
+            }
             c->fuse.*(o.field) = value;
             c->drop_graphs();   // captured steps hold the old launch configuration
             if (o.field == &FuseCfg::token_logprobs) {   // nothing has run under the new setting
                 c->lp_step_B = c->lp_run_B = c->lp_run_T = 0;
                 c->lp_run.clear();
                 c->lp_run_n.clear();
+            }
+            if (o.field == &FuseCfg::top_k) {
+                c->tk_step_B = c->tk_run_B = c->tk_run_T = 0;
+                c->tk_run_id.clear();
+                c->tk_run_lp.clear();
+                c->tk_run_n.clear();
             }
             HIPCHK(hipSetDevice(c->m->device));   // arrival counters back to rest
             const int rc = reset_counters(c);

@@ -36,6 +36,9 @@ struct StepRange {
     bool in(int g) const { return g >= lo && g < hi; }
 };
 static constexpr StepRange kWholeStep{0, 1 << 30};
+// option lmh_topk = 1: the fused top-K variant of the one-launch LM head up to this K (profiles/topk/topk_cost.txt: at 64
+// rows it beats the row kernel's path at K = 1 and 2 and loses from K = 4 on, its LDS insertion chain growing with K)
+static constexpr int kLmhTopkAutoMax = 2;
 static int step_layers(const qasr_ctx *c) { return c->dbg_layers > 0 ? c->dbg_layers : c->m->hp.dec_layers; }
 
 // one decode step for B sequences: token d_tok at position d_pos;
@@ -53,6 +56,12 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     // option token_logprobs: inside the one-launch LM head, else from the fp32 logits after the bookkeeping
     const bool lp = c->fuse.token_logprobs != 0;
     if (lp && !lmh_one) want_logits = true;
+    // option top_k: inside the one-launch LM head at 9 .. 64 rows where that measured faster (lmhead.hip TK; FuseCfg::lmh_topk);
+    // every other path writes its logits, then the row kernel after the bookkeeping (the one-launch heads write them too)
+    const bool tk = c->fuse.top_k > 0;
+    const bool tk_fused = tk && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && c->fuse.top_k <= kLmhTopkAutoMax));
+    if (tk && !tk_fused) want_logits = true;
+    int rc;
     const size_t layer_kv = (size_t)c->max_batch * hp.n_kv_head * c->max_ctx * 128;
     const int nl = step_layers(c);   // diagnostic layer cap
     // probed group (emitted alone): every launch in it folds its block times into one record
@@ -221,11 +230,18 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
             if (skinny) {   // amax / done are zero at rest: the LM head's last workgroup re-arms them
                 launch_gemv(EPI_ARGMAX, lm, s);
                 if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+                if (tk && (rc = topk_step(c, B))) return rc;
             } else {   // norm + GEMM + argmax + bookkeeping in one launch (lmhead.hip)
                 lm.nkv = c->d_nkv;
-                if (lp) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
+                // (the top-K variant carries the log-sum-exp code: d_lp / d_lphist are written with either option)
+                if (lp || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
+                if (tk_fused) {
+                    lm.tk_part = c->d_tkpart; lm.tk_out = c->d_tkid; lm.tk_lp = c->d_tklp; lm.tk_hist = c->d_tkhid;
+                    lm.tk_lphist = c->d_tkhlp; lm.tk_k = c->fuse.top_k;
+                }
                 if (!launch_lmhead_batch(lm, s))   // (lmh_one mirrors its shape conditions: never expected)
                     return fail(QASR_ERR_STATE, "decode step: the batched LM head declined B = " + std::to_string(B));
+                if (tk && !tk_fused && (rc = topk_step(c, B))) return rc;
             }
         } else {
             launch_fill_u64(c->d_amax, B, 0ull, s);
@@ -240,6 +256,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         launch_step_advance(c->d_pos, c->d_nkv, c->d_step, B, s);
         launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
         if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+        if (tk && (rc = topk_step(c, B))) return rc;
         launch_fill_u64(c->d_amax, B, 0ull, s);   // re-arm (zero at rest)
     }
     return declined_check("decode step");
@@ -467,6 +484,7 @@ extern "C" int qasr_decode_step(qasr_ctx *c, const int32_t *tok, const int *n_pa
     if (argmax) HIPCHK(hipMemcpyAsync(argmax, c->d_tok, B * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     c->lp_step_B = c->fuse.token_logprobs ? B : 0;
+    c->tk_step_B = c->fuse.top_k ? B : 0;
     return check_dev_err(c);
 }
 
@@ -477,6 +495,19 @@ extern "C" int qasr_get_step_logprobs(qasr_ctx *c, float *out, int B) {
     if (B < c->lp_step_B) return fail(QASR_ERR_ARG, "buffer shorter than the last step's batch");
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipMemcpyAsync(out, c->d_lp, (size_t)c->lp_step_B * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+extern "C" int qasr_get_step_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int K) {
+    if (!c || !ids || !logprobs || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.top_k) return fail(QASR_ERR_STATE, "option top_k is off");
+    if (K != c->fuse.top_k) return fail(QASR_ERR_ARG, "K differs from option top_k");
+    if (!c->tk_step_B) return fail(QASR_ERR_STATE, "no prefill or decode step has run with option top_k on");
+    if (B < c->tk_step_B) return fail(QASR_ERR_ARG, "buffer shorter than the last step's batch");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipMemcpyAsync(ids, c->d_tkid, (size_t)c->tk_step_B * K * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(logprobs, c->d_tklp, (size_t)c->tk_step_B * K * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }

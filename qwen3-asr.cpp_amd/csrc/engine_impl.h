@@ -157,6 +157,19 @@ struct qasr_ctx {
     std::vector<int> lp_run_n;     // ... and how many per row
     int lp_run_B = 0, lp_run_T = 0;
     const std::vector<float> *lp_sink = nullptr;   // inside a qasr_sink_fn call: the delivered clip's values
+    // option top_k (K = fuse.top_k): the last step's K alternatives per row [max_batch][K] as ids and
+    // log-probabilities, and their histories parallel to d_hist ([max_batch][hist_cap][K]); allocated for
+    // K = QASR_TOPK_MAX the first time the option is non-zero (ensure_topk), null until then
+    int32_t *d_tkid = nullptr, *d_tkhid = nullptr;
+    float *d_tklp = nullptr, *d_tkhlp = nullptr;
+    unsigned long long *d_tkpart = nullptr;   // the one-launch LM head's per-workgroup keys [lmhead_grid()][128][QASR_TOPK_MAX]
+    int tk_step_B = 0;                 // rows of the last qasr_prefill* / qasr_decode_step with the option on (0: none)
+    std::vector<int32_t> tk_run_id;    // the last qasr_run's alternatives [tk_run_B][tk_run_T][K], aligned with its tokens
+    std::vector<float> tk_run_lp;
+    std::vector<int> tk_run_n;         // ... and how many tokens per row
+    int tk_run_B = 0, tk_run_T = 0;
+    const std::vector<int32_t> *tk_sink_id = nullptr;   // inside a qasr_sink_fn call: the delivered clip's alternatives
+    const std::vector<float> *tk_sink_lp = nullptr;
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -244,6 +257,9 @@ int check_dev_err(qasr_ctx *c);
 std::mutex &device_lock(int device);
 int ensure(qasr_ctx *c, DevBuf &b, size_t bytes);
 int stage_pinned(qasr_ctx *c, const void *src, size_t bytes, void *dst);
+// option top_k after the greedy bookkeeping of a prefill or decode step (d_step names the slot of the
+// token just written to d_hist): the step's alternatives from the fp32 logits in d_logits
+int topk_step(qasr_ctx *c, int B);
 
 // V^T cache elements of one layer
 inline size_t layer_vt(const qasr_ctx *c) {

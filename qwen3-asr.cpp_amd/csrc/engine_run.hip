@@ -175,6 +175,23 @@ static int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const
         c->lp_run.assign((size_t)B * max_tokens, 0.f);
         c->lp_run_n.assign(B, 0);
     }
+    // option top_k: the same columns of its two histories, K entries a step
+    const int K = c->fuse.top_k;
+    std::vector<int32_t> tkid;
+    std::vector<float> tklp;
+    c->tk_run_B = 0;
+    if (K) {
+        tkid.resize((size_t)B * lp_cols * K);
+        tklp.resize(tkid.size());
+        HIPCHK(hipMemcpy2DAsync(tkid.data(), (size_t)lp_cols * K * 4, c->d_tkhid, (size_t)c->hist_cap * K * 4, (size_t)lp_cols * K * 4,
+                                B, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpy2DAsync(tklp.data(), (size_t)lp_cols * K * 4, c->d_tkhlp, (size_t)c->hist_cap * K * 4, (size_t)lp_cols * K * 4,
+                                B, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        c->tk_run_id.assign((size_t)B * max_tokens * K, -1);
+        c->tk_run_lp.assign((size_t)B * max_tokens * K, 0.f);
+        c->tk_run_n.assign(B, 0);
+    }
     if (c->profile_on) {   // the reference's QWEN3_TIMER sections (src/timing.h), device time
         auto add = [&](const char *name, hipEvent_t e0, hipEvent_t e1) -> int {
             float ms = 0.f;
@@ -207,14 +224,20 @@ static int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const
         for (int k = 0; k <= steps && k < max_tokens; k++) {
             const int32_t tk = hist[(size_t)b * c->hist_cap + k];
             if (lp) c->lp_run[(size_t)b * max_tokens + nt] = lph[(size_t)b * lp_cols + k];
+            for (int j = 0; j < K; j++) {
+                c->tk_run_id[((size_t)b * max_tokens + nt) * K + j] = tkid[((size_t)b * lp_cols + k) * K + j];
+                c->tk_run_lp[((size_t)b * max_tokens + nt) * K + j] = tklp[((size_t)b * lp_cols + k) * K + j];
+            }
             tokens[(size_t)b * max_tokens + nt++] = tk;
             if (!ignore_eos && tk == hp.eos_id) break;
         }
         if (!ignore_eos && nt > 0 && tokens[(size_t)b * max_tokens + nt - 1] == hp.eos_id) nt--;   // (its value goes with it)
         n_tokens[b] = nt;
         if (lp) c->lp_run_n[b] = nt;
+        if (K) c->tk_run_n[b] = nt;
     }
     if (lp) { c->lp_run_B = B; c->lp_run_T = max_tokens; }
+    if (K) { c->tk_run_B = B; c->tk_run_T = max_tokens; }
     if (t) {
         float a, b2, c2, d;
         (void)hipEventElapsedTime(&a, c->ev[EV_START], c->ev[EV_MEL]);
@@ -302,6 +325,8 @@ struct StreamSlot {
     int id = -1, P = 0, budget = 0;
     std::vector<int32_t> toks;
     std::vector<float> lps;   // option token_logprobs: one per token
+    std::vector<int32_t> tkid;   // option top_k: K per token
+    std::vector<float> tklp;
 };
 }  // namespace
 
@@ -341,20 +366,29 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
     int rc;
     const bool lp = c->fuse.token_logprobs != 0;
     c->lp_sink = nullptr;
+    const int K = c->fuse.top_k;
+    c->tk_sink_id = nullptr;
+    c->tk_sink_lp = nullptr;
     // a finished clip: trailing EOS popped (src/qwen3_asr.cpp:298-300)
     auto deliver = [&](StreamSlot &x) {
         std::vector<int32_t> &t = x.toks;
         if (!ignore_eos && !t.empty() && t.back() == hp.eos_id) {
             t.pop_back();
             if (lp) x.lps.pop_back();
+            if (K) { x.tkid.resize(x.tkid.size() - K); x.tklp.resize(x.tklp.size() - K); }
         }
         if (lp) c->lp_sink = &x.lps;   // qasr_stream_logprobs, for the length of the call
+        if (K) { c->tk_sink_id = &x.tkid; c->tk_sink_lp = &x.tklp; }   // qasr_stream_topk likewise
         sink(user, x.id, 0, t.data(), (int)t.size());
         c->lp_sink = nullptr;
+        c->tk_sink_id = nullptr;
+        c->tk_sink_lp = nullptr;
         st.n_clips++;
         x.id = -1;
         x.toks.clear();
         x.lps.clear();
+        x.tkid.clear();
+        x.tklp.clear();
     };
     auto reject = [&](int id, int code, const char *msg) {   // per-clip error: the message is qasr_last_error() inside sink
         fail(code, msg);
@@ -419,6 +453,12 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
             std::vector<float> first_lp(R);
             HIPCHK(hipMemcpyAsync(first.data(), c->d_tok, R * 4, hipMemcpyDeviceToHost, s));
             if (lp) HIPCHK(hipMemcpyAsync(first_lp.data(), c->d_lp, R * 4, hipMemcpyDeviceToHost, s));
+            std::vector<int32_t> first_tkid((size_t)R * K);
+            std::vector<float> first_tklp((size_t)R * K);
+            if (K) {
+                HIPCHK(hipMemcpyAsync(first_tkid.data(), c->d_tkid, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(first_tklp.data(), c->d_tklp, (size_t)R * K * 4, hipMemcpyDeviceToHost, s));
+            }
             HIPCHK(hipStreamSynchronize(s));   // (pcm host vector in flight until here)
             if ((rc = check_dev_err(c))) return rc;
             refilled = true;
@@ -436,6 +476,8 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                 x.budget = budgets[r];
                 x.toks.assign(1, first[r]);
                 x.lps.assign(lp ? 1 : 0, first_lp[r]);
+                x.tkid.assign(first_tkid.begin() + (size_t)r * K, first_tkid.begin() + (size_t)(r + 1) * K);
+                x.tklp.assign(first_tklp.begin() + (size_t)r * K, first_tklp.begin() + (size_t)(r + 1) * K);
                 if (c->tok_cb) c->tok_cb(c->tok_cb_user, x.id, 1, first[r]);
                 if ((!ignore_eos && first[r] == hp.eos_id) || x.budget == 1) deliver(x);
             }
@@ -444,6 +486,8 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
     std::vector<int> pos(S), nkv(S), tok(S);
     std::vector<int32_t> hist;
     std::vector<float> lph;
+    std::vector<int32_t> tkhid;
+    std::vector<float> tkhlp;
     if ((rc = decode_graph(c, S, false, 0))) return rc;
     for (;;) {
         if ((rc = refill())) return rc;
@@ -480,6 +524,14 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
             lph.resize((size_t)S * chunk);
             HIPCHK(hipMemcpy2DAsync(lph.data(), chunk * 4, c->d_lphist + 1, (size_t)c->hist_cap * 4, chunk * 4, Bq, hipMemcpyDeviceToHost, s));
         }
+        if (K) {   // likewise, K entries a step
+            tkhid.resize((size_t)S * chunk * K);
+            tkhlp.resize(tkhid.size());
+            HIPCHK(hipMemcpy2DAsync(tkhid.data(), (size_t)chunk * K * 4, c->d_tkhid + K, (size_t)c->hist_cap * K * 4, (size_t)chunk * K * 4,
+                                    Bq, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpy2DAsync(tkhlp.data(), (size_t)chunk * K * 4, c->d_tkhlp + K, (size_t)c->hist_cap * K * 4, (size_t)chunk * K * 4,
+                                    Bq, hipMemcpyDeviceToHost, s));
+        }
         HIPCHK(hipStreamSynchronize(s));   // (the pos / nkv / tok host vectors in flight until here)
         if ((rc = check_dev_err(c))) return rc;
         st.t_decode_ms += ms_since(t0);
@@ -493,6 +545,11 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                 const int32_t t = hist[(size_t)i * chunk + k];
                 x.toks.push_back(t);
                 if (lp) x.lps.push_back(lph[(size_t)i * chunk + k]);
+                if (K) {
+                    const size_t o = ((size_t)i * chunk + k) * K;
+                    x.tkid.insert(x.tkid.end(), tkhid.begin() + o, tkhid.begin() + o + K);
+                    x.tklp.insert(x.tklp.end(), tkhlp.begin() + o, tkhlp.begin() + o + K);
+                }
                 st.live_steps++;
                 if (c->tok_cb) c->tok_cb(c->tok_cb_user, x.id, (int)x.toks.size(), t);
                 if ((!ignore_eos && t == hp.eos_id) || (int)x.toks.size() >= x.budget) {
@@ -547,6 +604,37 @@ extern "C" int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap) {
     const int n = (int)c->lp_sink->size();
     if (cap < n) return -fail(QASR_ERR_ARG, "buffer shorter than the clip's tokens");
     for (int k = 0; k < n; k++) out[k] = (*c->lp_sink)[k];
+    return n;
+}
+
+extern "C" int qasr_get_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int max_tokens, int K) {
+    if (!c || !ids || !logprobs || B <= 0 || max_tokens <= 0) return fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.top_k) return fail(QASR_ERR_STATE, "option top_k is off");
+    if (K != c->fuse.top_k) return fail(QASR_ERR_ARG, "K differs from option top_k");
+    if (!c->tk_run_B) return fail(QASR_ERR_STATE, "no run has finished with option top_k on");
+    if (B < c->tk_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
+    for (int b = 0; b < c->tk_run_B; b++)
+        if (c->tk_run_n[b] > max_tokens) return fail(QASR_ERR_ARG, "buffer rows shorter than the last run's tokens");
+    for (int b = 0; b < c->tk_run_B; b++)
+        for (size_t k = 0; k < (size_t)c->tk_run_n[b] * K; k++) {
+            ids[(size_t)b * max_tokens * K + k] = c->tk_run_id[(size_t)b * c->tk_run_T * K + k];
+            logprobs[(size_t)b * max_tokens * K + k] = c->tk_run_lp[(size_t)b * c->tk_run_T * K + k];
+        }
+    return 0;
+}
+
+// (a count on success, so errors are minus the code, as qasr_stream_logprobs)
+extern "C" int qasr_stream_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int cap_tokens, int K) {
+    if (!c || cap_tokens < 0 || (cap_tokens > 0 && (!ids || !logprobs))) return -fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->fuse.top_k) return -fail(QASR_ERR_STATE, "option top_k is off");
+    if (K != c->fuse.top_k) return -fail(QASR_ERR_ARG, "K differs from option top_k");
+    if (!c->tk_sink_id) return -fail(QASR_ERR_STATE, "qasr_stream_topk is valid only inside a qasr_sink_fn call");
+    const int n = (int)(c->tk_sink_id->size() / K);
+    if (cap_tokens < n) return -fail(QASR_ERR_ARG, "buffer shorter than the clip's tokens");
+    for (size_t k = 0; k < (size_t)n * K; k++) {
+        ids[k] = (*c->tk_sink_id)[k];
+        logprobs[k] = (*c->tk_sink_lp)[k];
+    }
     return n;
 }
 

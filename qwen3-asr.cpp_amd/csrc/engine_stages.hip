@@ -403,7 +403,7 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     launch_rmsnorm_f16(x, H, c->plast.as<int>(), B, H, m->out_norm, hp.rms_eps, xl, s);
     launch_fill_u64(c->d_amax, B, 0ull, s);
     const bool lp = c->fuse.token_logprobs != 0;   // the log-probabilities come from the fp32 logits
-    want_logits = want_logits || lp;
+    want_logits = want_logits || lp || c->fuse.top_k > 0;   // (option top_k: its alternatives likewise)
     if (B <= 8) {
         GemvArgs gv{};
         gv.xh = xl; gv.ldxh = H; gv.W = m->embd; gv.K = H; gv.N = hp.vocab; gv.M = B;
@@ -418,6 +418,7 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     HIPCHK(hipMemsetAsync(c->d_step, 0, 4, s));
     launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
     if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+    if ((rc = topk_step(c, B))) return rc;
     launch_fill_u64(c->d_amax, B, 0ull, s);   // zero at rest for the decode graph
     // decode state: next position = P_b, n_kv = P_b + 1 (the fed token's own key included)
     std::vector<int> pos(B), nkv(B);
@@ -636,6 +637,7 @@ static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, c
     if (argmax) HIPCHK(hipMemcpyAsync(argmax, c->d_tok, B * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     c->lp_step_B = c->fuse.token_logprobs ? B : 0;
+    c->tk_step_B = c->fuse.top_k ? B : 0;
     return 0;
 }
 

@@ -141,6 +141,10 @@ struct GemvArgs {
     // per-workgroup packed (m, s) partials [grid][128] (lmhead_grid() workgroups), the step's
     // log-probability of each row's argmax [M], and its history parallel to hist (hist_stride)
     unsigned long long *lp_part; float *lp_out; float *lp_hist;
+    // launch_lmhead_batch, 9 .. 64 rows, top-K alternatives (all or none, with the lp_* group set; null = off):
+    // per-workgroup sorted keys [grid][128][TOPK_MAX], the step's tk_k (1 .. TOPK_MAX) ids and
+    // log-probabilities a row [M][tk_k], and their histories parallel to hist ([row][hist_stride][tk_k])
+    unsigned long long *tk_part; int32_t *tk_out; float *tk_lp; int32_t *tk_hist; float *tk_lphist; int tk_k;
 };
 void launch_gemv(int epi, const GemvArgs &g, hipStream_t s);
 // lmhead.hip: decode-batch LM head in one launch (9..128 rows; K = 1024, f16 W):
@@ -207,6 +211,13 @@ struct FuseCfg {
     int token_logprobs = 0;             // every greedy step also yields the log-probability of its argmax token
                                         // (qasr_get_*logprobs): in the one-launch LM head where that runs (lmhead.hip
                                         // LSE), else from the fp32 logits by launch_token_logprob; 0: nothing changes
+    int lmh_topk = 1;                   // diagnostic, option top_k at 9 .. 64 rows: 2 = always inside the one-launch LM head
+                                        // (lmhead.hip TK), 0 = never (that launch writes its logits and launch_topk_rows reads
+                                        // them, as at 65 .. 128 rows), 1 = whichever measured faster at this K (engine_decode.hip)
+    int top_k = 0;                      // K in 1 .. TOPK_MAX: every greedy step also yields its K largest logits as
+                                        // (id, log-probability) pairs (qasr_get_*topk): from the fp32 logits by
+                                        // launch_topk_rows (the step then writes its logits), or inside the one-launch
+                                        // LM head (lmh_topk above); 0: nothing changes
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
@@ -387,6 +398,14 @@ void launch_fill_u64(unsigned long long *p, int n, unsigned long long v, hipStre
 // n_valid = 0: every column
 void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const int32_t *tok, const int *step, float *lp_out,
                           float *lp_hist, int hist_stride, hipStream_t s);
+// the K (1 .. TOPK_MAX) largest logits of each row of the fp32 logits [B][ld], descending, equal values by
+// lower column first (entry 0 is the greedy token), as ids and log-probabilities
+// logit - logsumexp(logits[b][0 .. n_valid)): to tk_ids / tk_lp [B][K] and, where the histories are
+// non-null, to tk_hist_* [b][*step][K] (rows of hist_stride steps, the slot of the token just
+// written to hist); n_valid = 0: every column.  false = K out of range (nothing launched)
+constexpr int TOPK_MAX = 8;
+bool launch_topk_rows(const float *logits, int ld, int B, int n_valid, int K, const int *step, int32_t *tk_ids, float *tk_lp,
+                      int32_t *tk_hist_ids, float *tk_hist_lp, int hist_stride, hipStream_t s);
 // dst row r = src row idx[r], fp32 rows of D floats (D % 4 == 0)
 void launch_gather_rows(const float *src, const int *idx, int rows, int D, float *dst, hipStream_t s);
 // decode-step bookkeeping on device: n_kv[b] += 1, row_pos[b] += 1, step += 1

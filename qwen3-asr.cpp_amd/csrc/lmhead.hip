@@ -38,6 +38,12 @@
 // and writes lp_out / lp_hist next to tok_out / hist.  No floating-point
 // atomics: the value does not depend on arrival order.  LSE = false is the
 // kernel as it was.
+//
+// TK = true (GemvArgs::tk_part set, option top_k; lmhead_batch_kernel only,
+// implies LSE) adds the K largest keys of every row: each workgroup keeps a
+// sorted K-list a row in LDS (tk_insert), publishes it beside its (m, s), and
+// the last workgroup merges the lists behind the K largest slot-0 keys
+// (tk_finish).  TK = false is the kernel as it was.
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -59,8 +65,9 @@ __device__ __forceinline__ int lmh_off(int row, int k) {   // element offset of 
 // last workgroup, every thread: row tid / LPR's (m, s) over the G workgroups' partials, 16 loads in
 // flight a lane; then the log-probability of the row's argmax (the value in its amax key, still
 // armed) to lp_out / lp_hist[row][st + 1]
+// (ms_out non-null, the top-K variant: the row's (m, s) is left there too)
 template <int LPR>
-__device__ __forceinline__ void lse_finish(const GemvArgs &g, int M, int G, int st) {
+__device__ __forceinline__ void lse_finish(const GemvArgs &g, int M, int G, int st, float2 *ms_out = nullptr) {
     const int tid = threadIdx.x, row = tid / LPR, sub = tid % LPR;
     float m = -INFINITY, s = 0.f;
     if (row < M) {
@@ -92,19 +99,80 @@ __device__ __forceinline__ void lse_finish(const GemvArgs &g, int M, int G, int 
         const float lp = lse_logprob(argmax_key_val(k), m, s);
         g.lp_out[row] = lp;
         g.lp_hist[(long)row * g.hist_stride + st + 1] = lp;
+        if (ms_out) ms_out[row] = make_float2(m, s);
     }
 }
 
-template <int MT, int WPG, int D, bool LSE>
+// ---- top-K alternatives (TK = true, GemvArgs::tk_part set, option top_k) ----
+// A sorted list of K distinct keys in LDS, slot 0 the largest, kept by a chain of
+// 64-bit atomicMax: slot j keeps the larger of its key and the arriving one and
+// the smaller carries on to slot j + 1.  Every key that ever reaches slot j but
+// its final maximum leaves it exactly once, so slot j ends with the (j + 1)-th
+// largest key inserted, whatever the order of arrival.
+__device__ __forceinline__ void tk_insert(unsigned long long *list, unsigned long long k, int K) {
+    for (int j = 0; j < K && k != 0ull; j++) {
+        const unsigned long long old = atomicMax(list + j, k);
+        k = old < k ? old : k;
+    }
+}
+// the list's K-th key (0 while it is not full): no key below it can enter any more.  A stale read is lower, so conservative.
+__device__ __forceinline__ unsigned long long tk_kth(const unsigned long long *list, int K) {
+    return __hip_atomic_load(list + K - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+constexpr int TKS = 8;   // list stride (TOPK_MAX)
+
+// last workgroup, every thread (row tid / LPR, lane sub of LPR >= K): the K largest of the row's G slot-0
+// keys (lists are sorted: only the workgroups behind them can hold one of the row's K largest keys; a key's
+// column names its workgroup), then the K largest of those <= K lists' keys, as ids and log-probabilities
+// with the row's (m, s) from lse_finish.  l1 / l2: two zeroed LDS lists a row.
+template <int LPR, int WPG>
+__device__ __forceinline__ void tk_finish(const GemvArgs &g, int M, int G, int st, unsigned long long *l1, unsigned long long *l2,
+                                          const float2 *ms) {
+    const int tid = threadIdx.x, row = tid / LPR, sub = tid % LPR, K = g.tk_k;
+    if (row < M) {
+        for (int w = sub; w < G; w += LPR) {
+            const unsigned long long k = __hip_atomic_load(g.tk_part + ((long)w * 128 + row) * TKS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (k > tk_kth(l1 + row * TKS, K)) tk_insert(l1 + row * TKS, k, K);
+        }
+    }
+    __syncthreads();
+    if (row < M && sub < K) {
+        const unsigned long long k0 = l1[row * TKS + sub];
+        if (k0) {
+            const long U = g.N >> 4, TW = (long)G * WPG, u = argmax_key_idx(k0) >> 4;
+            const int w = (int)((((u + 1) * TW + U - 1) / U - 1) / WPG);   // the wave whose units [gw U / TW, (gw + 1) U / TW) hold u
+            for (int j = 0; j < K; j++)
+                tk_insert(l2 + row * TKS, __hip_atomic_load(g.tk_part + ((long)w * 128 + row) * TKS + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), K);
+        }
+    }
+    __syncthreads();
+    if (row < M && sub < K) {
+        const unsigned long long k = l2[row * TKS + sub];
+        const int id = k ? argmax_key_idx(k) : -1;
+        const float lp = k ? lse_logprob(argmax_key_val(k), ms[row].x, ms[row].y) : -INFINITY;
+        g.tk_out[(long)row * K + sub] = id;
+        g.tk_lp[(long)row * K + sub] = lp;
+        const long h = ((long)row * g.hist_stride + st + 1) * K + sub;
+        g.tk_hist[h] = id;
+        g.tk_lphist[h] = lp;
+    }
+}
+
+template <int MT, int WPG, int D, bool LSE, bool TK>
 __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
+    static_assert(LSE || !TK, "the top-K variant carries the log-sum-exp code");
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];   // [MT*16][LMH_K] fp16, swizzled
     __shared__ unsigned long long bestk[WPG][MT * 16];
     __shared__ float2 lsek[LSE ? WPG : 1][LSE ? MT * 16 : 1];
+    __shared__ unsigned long long tk[TK ? MT * 16 * TKS : 1], tk2[TK ? MT * 16 * TKS : 1];   // TK: the workgroup's K keys a row
     __shared__ int last_wg, st;
     stamp_start(g.stamp);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int q = lane >> 4, c16 = lane & 15;
     const int M = g.M;
+    if constexpr (TK) {   // (visible after the prologue's barrier)
+        for (int e = tid; e < MT * 16 * TKS; e += 64 * WPG) tk[e] = 0ull;
+    }
 
     // ---- this wave's units (16 weight rows each) and items (unit, 128-wide K chunk)
     const int U = g.N >> 4, TW = gridDim.x * WPG, gw = blockIdx.x * WPG + wid;
@@ -213,6 +281,14 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
                         if constexpr (LSE) {
                             if (col < nvalid) lse_add(lm[i][r], ls[i][r], v);
                         }
+                        if constexpr (TK) {
+                            // against the list's K-th key as it is now, not as of the last unit: the eight waves finish
+                            // their units at different times, and the later ones find the list the earlier ones filled
+                            // (a full-key compare: a key below the K-th can never enter, an equal value with a lower
+                            // column is above it)
+                            unsigned long long *list = tk + (row < M ? row : 0) * TKS;
+                            if (col < nvalid && row < M && key > tk_kth(list, g.tk_k)) tk_insert(list, key, g.tk_k);
+                        }
                     }
             }
         }
@@ -251,18 +327,30 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
             __hip_atomic_store(g.lp_part + (long)blockIdx.x * 128 + tid, lse_pack(m, s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    if constexpr (TK) {   // this workgroup's K keys a row (complete at the barrier above), published as lp_part is
+        for (int e = tid; e < M * TKS; e += 64 * WPG)
+            if ((e & (TKS - 1)) < g.tk_k)
+                __hip_atomic_store(g.tk_part + (long)blockIdx.x * 128 * TKS + e, tk[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) last_wg = __hip_atomic_fetch_add(g.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
     __syncthreads();
     if (last_wg) {
         if (tid == 0) st = *g.step;
+        if constexpr (TK) {   // (every thread is past its publication: the lists are free)
+            for (int e = tid; e < MT * 16 * TKS; e += 64 * WPG) tk[e] = tk2[e] = 0ull;
+        }
         __syncthreads();
         if constexpr (LSE) {
             constexpr int LPR = MT == 1 ? 32 : MT == 2 ? 16 : 8;   // lanes a row: 64 WPG threads over MT * 16 rows
             static_assert(LPR * MT * 16 <= 64 * WPG, "a lane group for every row");
-            lse_finish<LPR>(g, M, gridDim.x, st);
+            lse_finish<LPR>(g, M, gridDim.x, st, TK ? &lsek[0][0] : nullptr);
             __syncthreads();   // amax read before it is re-armed below
+            if constexpr (TK) {
+                static_assert(LPR >= TKS, "a lane for each of a row's K keys");
+                tk_finish<LPR, WPG>(g, M, gridDim.x, st, tk, tk2, &lsek[0][0]);
+            }
         }
         if (tid < M) {
             const unsigned long long k = __hip_atomic_load(g.amax + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -284,7 +372,7 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
 // 8 waves a CU with a 4-deep ring (tools/micro/lmh_bench.hip, MI355X: 16 rows
 // 60.8 us against 68.9 with 16 waves x 3; 64 rows: 6- and 8-deep rings and 4
 // waves x 8 or 12 slower)
-template <int MT, bool LSE, int WPG = 8, int D = 4>
+template <int MT, bool LSE, bool TK, int WPG = 8, int D = 4>
 void run_lmhead_v(const GemvArgs &g, hipStream_t s) {
     static int ncu_dev[64];   // per device: CU count once the LDS attribute is set
     int dev = 0;
@@ -293,16 +381,17 @@ void run_lmhead_v(const GemvArgs &g, hipStream_t s) {
     if (!ncu) {
         int n = 0;
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipFuncSetAttribute((const void *)lmhead_batch_kernel<MT, WPG, D, LSE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)lmhead_batch_kernel<MT, WPG, D, LSE, TK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   MT * 16 * LMH_K * 2);
         ncu = n > 0 ? n : 256;
     }
-    hipLaunchKernelGGL((lmhead_batch_kernel<MT, WPG, D, LSE>), dim3(ncu), dim3(64 * WPG), MT * 16 * LMH_K * 2, s, g);
+    hipLaunchKernelGGL((lmhead_batch_kernel<MT, WPG, D, LSE, TK>), dim3(ncu), dim3(64 * WPG), MT * 16 * LMH_K * 2, s, g);
 }
 template <int MT>
 void run_lmhead(const GemvArgs &g, hipStream_t s) {
-    if (g.lp_part) run_lmhead_v<MT, true>(g, s);
-    else run_lmhead_v<MT, false>(g, s);
+    if (g.tk_part) run_lmhead_v<MT, true, true>(g, s);
+    else if (g.lp_part) run_lmhead_v<MT, true, false>(g, s);
+    else run_lmhead_v<MT, false, false>(g, s);
 }
 
 // ---- 65..128 rows in one launch, the embedding read once (round 6).  The
@@ -516,6 +605,11 @@ bool launch_lmhead_batch(const GemvArgs &g, hipStream_t s) {
         !g.step || !g.pos || g.Wd)
         return false;
     if ((g.lp_part || g.lp_out || g.lp_hist) && !(g.lp_part && g.lp_out && g.lp_hist && g.hist_stride > 0)) return false;
+    // top-K pointers: all or none, 9 .. 64 rows only (lmhead128_kernel has no such variant), on top of the lp_* group
+    const bool tk_any = g.tk_part || g.tk_out || g.tk_lp || g.tk_hist || g.tk_lphist;
+    if (tk_any && !(g.tk_part && g.tk_out && g.tk_lp && g.tk_hist && g.tk_lphist && g.lp_part && g.tk_k >= 1 && g.tk_k <= TKS &&
+                    g.M <= 64))
+        return false;
     if (g.M > 64) {   // 65..128 rows: the rows in registers, the embedding read once (round 6; until then one
                       // launch per 64-row half, each streaming all 311 MB: tools/micro/lmh128_bench)
         if (g.lp_part) run_lmhead128<true>(g, s);

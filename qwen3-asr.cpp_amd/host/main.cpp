@@ -33,6 +33,7 @@ struct cli_params {
     std::vector<int> devices;   // --devices: shard the files over these GPUs
     bool print_progress = false, print_timing = true, print_tokens = false, profile = false;
     bool logprobs = false;   // --logprobs: per-token log-probabilities (transcribe_params::token_logprobs)
+    int32_t top_k = 0;       // --top-k: alternatives per token (transcribe_params::top_k)
     bool align_mode = false, transcribe_align_mode = false;
 };
 
@@ -48,6 +49,7 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --no-timing            Don't print timing information\n");
     fprintf(stderr, "  --tokens               Print token IDs\n");
     fprintf(stderr, "  --logprobs             Per-token log-probabilities: avg / min per file, and with --tokens each token's\n");
+    fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
     fprintf(stderr, "  --profile              Print timing profile\n");
     fprintf(stderr, "  --device <n>           HIP device index (default: 0)\n");
     fprintf(stderr, "  --file-list <path>     Text file with one audio path per line (added to the -f files)\n");
@@ -103,6 +105,11 @@ static bool parse(int argc, char **argv, cli_params &p) {
         else if (!strcmp(a, "--no-timing")) p.print_timing = false;
         else if (!strcmp(a, "--tokens")) p.print_tokens = true;
         else if (!strcmp(a, "--logprobs")) p.logprobs = true;
+        else if (!strcmp(a, "--top-k")) {
+            if (!val(v)) return false;
+            p.top_k = atoi(v.c_str());
+            if (p.top_k < 1 || p.top_k > 8) { fprintf(stderr, "Error: --top-k takes 1..8\n"); return false; }
+        }
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
         else if (!strcmp(a, "-a") || !strcmp(a, "--transcribe-align")) p.transcribe_align_mode = true;
@@ -403,6 +410,7 @@ static int run_transcription(const cli_params &p) {
     tp.print_progress = p.print_progress;
     tp.print_timing = p.print_timing;
     tp.token_logprobs = p.logprobs;
+    tp.top_k = p.top_k;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));
@@ -427,6 +435,11 @@ static int run_transcription(const cli_params &p) {
             for (size_t k = 0; k < r.tokens.size(); ++k) {
                 if (lp) fprintf(stderr, "  [%zu] %d %.4f\n", k, r.tokens[k], r.token_logprobs[k]);
                 else fprintf(stderr, "  [%zu] %d\n", k, r.tokens[k]);
+                if (p.top_k > 0 && r.alt_tokens.size() == r.tokens.size() * p.top_k)
+                    for (int j = 0; j < p.top_k; j++) {
+                        const int32_t id = r.alt_tokens[k * p.top_k + j];
+                        fprintf(stderr, "        %d  %.4f  \"%s\"\n", id, r.alt_logprobs[k * p.top_k + j], asr.token_text(id).c_str());
+                    }
             }
             fprintf(stderr, "\n");
         }

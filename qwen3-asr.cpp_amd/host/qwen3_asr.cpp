@@ -111,6 +111,17 @@ bool Qwen3ASR::set_logprobs(bool on) {
     return true;
 }
 
+// context option top_k likewise
+bool Qwen3ASR::set_top_k(int k) {
+    int cur = 0;
+    if (qasr_ctx_get_option(ctx_, "top_k", &cur) == 0 && cur == k) return true;
+    if (qasr_ctx_set_option(ctx_, "top_k", k) != 0) {
+        error_msg_ = std::string("Failed to set top_k: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
 transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const transcribe_params &params) {
     transcribe_result result;
     if (!model_) { result.error_msg = "Model not loaded"; return result; }
@@ -155,7 +166,8 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         sys.resize(std::max(k, 0));
         qasr_tokenize(model_, params.system_prompt.c_str(), sys.data(), k);
     }
-    if (!ensure_ctx(B, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs)) {
+    if (!ensure_ctx(B, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
+        !set_top_k(params.top_k)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -188,12 +200,28 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
             return out;
         }
     }
+    const int K = params.top_k;
+    std::vector<int32_t> alt_id;
+    std::vector<float> alt_lp;
+    if (K > 0) {
+        alt_id.resize((size_t)B * params.max_tokens * K);
+        alt_lp.resize(alt_id.size());
+        if (qasr_get_topk(ctx_, alt_id.data(), alt_lp.data(), B, params.max_tokens, K) != 0) {
+            for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+            return out;
+        }
+    }
     const int64_t t1 = now_ms();
     for (int b = 0; b < B; b++) {
         transcribe_result &r = out[b];
         r.tokens.assign(toks.begin() + (long)b * params.max_tokens, toks.begin() + (long)b * params.max_tokens + nt[b]);
         if (params.token_logprobs)
             r.token_logprobs.assign(lps.begin() + (long)b * params.max_tokens, lps.begin() + (long)b * params.max_tokens + nt[b]);
+        if (K > 0) {
+            const long o = (long)b * params.max_tokens * K;
+            r.alt_tokens.assign(alt_id.begin() + o, alt_id.begin() + o + (long)nt[b] * K);
+            r.alt_logprobs.assign(alt_lp.begin() + o, alt_lp.begin() + o + (long)nt[b] * K);
+        }
         const int len = qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), nullptr, 0);
         std::string text(std::max(len, 0) + 1, '\0');
         qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), &text[0], (int)text.size());
@@ -243,6 +271,8 @@ struct StreamCtx {
     std::vector<float> pcm;
     int64_t t0;
     qasr_ctx *lp_ctx;   // non-null: transcribe_params::token_logprobs
+    qasr_ctx *tk_ctx;   // non-null: transcribe_params::top_k, its value in top_k
+    int top_k;
 };
 int stream_fetch(void *u, const float **pcm, int *n, int *) {
     StreamCtx *s = (StreamCtx *)u;
@@ -262,6 +292,14 @@ void stream_sink(void *u, int id, int status, const int32_t *toks, int n) {
         if (s->lp_ctx) {
             r.token_logprobs.resize(n);
             if (qasr_stream_logprobs(s->lp_ctx, r.token_logprobs.data(), n) != n) r.token_logprobs.clear();
+        }
+        if (s->tk_ctx) {
+            r.alt_tokens.resize((size_t)n * s->top_k);
+            r.alt_logprobs.resize((size_t)n * s->top_k);
+            if (qasr_stream_topk(s->tk_ctx, r.alt_tokens.data(), r.alt_logprobs.data(), n, s->top_k) != n) {
+                r.alt_tokens.clear();
+                r.alt_logprobs.clear();
+            }
         }
         const int len = qasr_detokenize(s->model, toks, n, nullptr, 0);
         std::string text(std::max(len, 0) + 1, '\0');
@@ -289,13 +327,14 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     // chunking unit) plus the budget -- longer clips fail alone ("Context length")
     const int need = n_ctx > 0 ? n_ctx : qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(30 * 16000))) + (int)sys.size() + params.max_tokens;
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
-    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs)) return false;
+    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k)) return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
     const bool per_token = progress_callback_ || params.print_progress;
     qasr_set_token_callback(ctx_, per_token ? stream_token_cb : nullptr, per_token ? &tcb : nullptr);
-    StreamCtx sc{&fetch, &sink, model_, {}, now_ms(), params.token_logprobs ? ctx_ : nullptr};
+    StreamCtx sc{&fetch, &sink, model_, {}, now_ms(), params.token_logprobs ? ctx_ : nullptr,
+                 params.top_k > 0 ? ctx_ : nullptr, params.top_k};
     const int rc = qasr_run_stream(ctx_, S, stream_fetch, stream_sink, &sc, params.max_tokens, 0, nullptr);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
     if (rc != 0) { error_msg_ = std::string("Decoding failed: ") + qasr_last_error(); return false; }
@@ -321,6 +360,15 @@ transcribe_result Qwen3ASR::transcribe_internal(const float *samples, int n_samp
         fprintf(stderr, "  Tokens generated: %zu\n", r.tokens.size());
     }
     return r;
+}
+
+std::string Qwen3ASR::token_text(int32_t id) const {
+    if (!model_) return std::string();
+    const int len = qasr_detokenize(model_, &id, 1, nullptr, 0);
+    std::string text(std::max(len, 0) + 1, '\0');
+    qasr_detokenize(model_, &id, 1, &text[0], (int)text.size());
+    text.resize(std::max(len, 0));
+    return text;
 }
 
 void Qwen3ASR::set_progress_callback(progress_callback_t callback) { progress_callback_ = std::move(callback); }

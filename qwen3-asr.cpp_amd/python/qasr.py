@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -35,6 +35,7 @@ EXPORTS = [
     "qasr_align_prompt_len", "qasr_align_json", "qasr_align_json_batch", "qasr_align_words",
     "qasr_ctx_grow_shape",
     "qasr_get_step_logprobs", "qasr_get_logprobs", "qasr_stream_logprobs",
+    "qasr_get_step_topk", "qasr_get_topk", "qasr_stream_topk",
 ]
 
 
@@ -114,6 +115,8 @@ def lib() -> C.CDLL:
             "qasr_debug_read": ([P, C.c_char_p, P, C.c_int64], I),
             "qasr_get_step_logprobs": ([P, F, I], I), "qasr_get_logprobs": ([P, F, I, I], I),
             "qasr_stream_logprobs": ([P, F, I], I),
+            "qasr_get_step_topk": ([P, I32P, F, I, I], I), "qasr_get_topk": ([P, I32P, F, I, I, I], I),
+            "qasr_stream_topk": ([P, I32P, F, I, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -291,23 +294,36 @@ class RunResult:
     timings: Timings
     # log-probability of every token (context option "token_logprobs"), the shape of tokens; None with the option off
     logprobs: Optional[List[List[float]]] = None
+    # the K most likely tokens of every step (context option "top_k"): per row (ids [n][K] int32, logprobs [n][K]
+    # float32), n the row's tokens and entry 0 of a step the token itself; None with the option off
+    topk: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None
 
 
-def _sink_into(out: dict, failed: list, ctx=None):
+def _sink_into(out: dict, failed: list, ctx=None, tk_ctx=None):
     """ctx: the running context when the caller asked for log-probabilities --
-    the sink then stores (tokens, logprobs) per clip (qasr_stream_logprobs)"""
+    the sink then stores (tokens, logprobs) per clip (qasr_stream_logprobs);
+    tk_ctx: likewise for the top-K alternatives -- (ids [n][K], logprobs
+    [n][K]) is appended to the clip's tuple (qasr_stream_topk)"""
     def sink(_u, cid, status, toks, n):
         try:
             if status:
                 out[cid] = QasrError(lib().qasr_last_error().decode(errors="replace"))
-            elif ctx is not None:
+                return
+            item = [[int(toks[i]) for i in range(n)]]
+            if ctx is not None:
                 lp = np.zeros(max(n, 1), np.float32)
                 k = lib().qasr_stream_logprobs(ctx.h, _f(lp), n)
                 if k != n:
                     raise QasrError(f"qasr_stream_logprobs: {lib().qasr_last_error().decode(errors='replace')}")
-                out[cid] = ([int(toks[i]) for i in range(n)], lp[:n].tolist())
-            else:
-                out[cid] = [int(toks[i]) for i in range(n)]
+                item.append(lp[:n].tolist())
+            if tk_ctx is not None:
+                K = max(tk_ctx.get_option("top_k"), 1)
+                ids, lps = np.zeros((max(n, 1), K), np.int32), np.zeros((max(n, 1), K), np.float32)
+                k = lib().qasr_stream_topk(tk_ctx.h, _i32(ids), _f(lps), n, K)
+                if k != n:
+                    raise QasrError(f"qasr_stream_topk: {lib().qasr_last_error().decode(errors='replace')}")
+                item.append((ids[:n], lps[:n]))
+            out[cid] = item[0] if len(item) == 1 else tuple(item)
         except BaseException as e:   # (ctypes would swallow it)
             failed.append(e)
     return sink
@@ -452,7 +468,8 @@ class Context:
         nt = np.zeros(B, np.int32)
         t = Timings()
         _check(lib().qasr_run(self.h, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)), "qasr_run")
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens))
+        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
+                         self._run_topk(nt, max_tokens))
 
     def _run_logprobs(self, nt, max_tokens: int):
         """the last run's log-probabilities per row (None with option token_logprobs off)"""
@@ -462,6 +479,23 @@ class Context:
         lp = np.zeros((B, max_tokens), np.float32)
         _check(lib().qasr_get_logprobs(self.h, _f(lp), B, max_tokens), "qasr_get_logprobs")
         return [lp[b, :nt[b]].tolist() for b in range(B)]
+
+    def _run_topk(self, nt, max_tokens: int):
+        """the last run's top-K alternatives per row (None with option top_k off)"""
+        K = self.get_option("top_k")
+        if not K:
+            return None
+        B = len(nt)
+        ids, lps = np.zeros((B, max_tokens, K), np.int32), np.zeros((B, max_tokens, K), np.float32)
+        _check(lib().qasr_get_topk(self.h, _i32(ids), _f(lps), B, max_tokens, K), "qasr_get_topk")
+        return [(ids[b, :nt[b]].copy(), lps[b, :nt[b]].copy()) for b in range(B)]
+
+    def step_topk(self, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(ids [B][K], logprobs [B][K]) of the last prefill / decode_step (option top_k = K)"""
+        K = max(self.get_option("top_k"), 1)
+        ids, lps = np.zeros((B, K), np.int32), np.zeros((B, K), np.float32)
+        _check(lib().qasr_get_step_topk(self.h, _i32(ids), _f(lps), B, K), "qasr_get_step_topk")
+        return ids, lps
 
     def step_logprobs(self, B: int) -> np.ndarray:
         """log-probability of each row's argmax of the last prefill / decode_step (option token_logprobs)"""
@@ -478,15 +512,18 @@ class Context:
         t = Timings()
         _check(lib().qasr_run_staged(self.h, _i(idx), B, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)),
                "qasr_run_staged")
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens))
+        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
+                         self._run_topk(nt, max_tokens))
 
-    def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0, logprobs: bool = False):
+    def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0, logprobs: bool = False,
+                   topk: bool = False):
         """Continuous batching (qasr_run_stream): next_clip() -> (id, pcm[, budget])
         or None when the queue is empty; returns ({id: tokens | QasrError},
         StreamStats).  Slots (0: max_batch) freed by a finished clip are
         refilled at the next chunk boundary; a clip that fails alone maps to
         its QasrError.  logprobs=True (option token_logprobs on): a clip maps
-        to (tokens, logprobs) instead."""
+        to (tokens, logprobs) instead.  topk=True (option top_k on) appends
+        (ids [n][K], logprobs [n][K]) to that tuple."""
         out, keep = {}, []
 
         def fetch(_u, pcm_pp, n_p, budget_p):
@@ -502,7 +539,8 @@ class Context:
             return cid
 
         failed = []
-        f, k = FETCH_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None))
+        f, k = FETCH_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None,
+                                                                                     self if topk else None))
         st = StreamStats()
         rc = lib().qasr_run_stream(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
         if failed:
@@ -511,7 +549,7 @@ class Context:
         return out, st
 
     def run_stream_staged(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0,
-                          logprobs: bool = False):
+                          logprobs: bool = False, topk: bool = False):
         """run_stream over the staged pool (stage_audio): next_clip() -> staged
         index (its id) or (index, budget), None when the queue is empty"""
         out = {}
@@ -526,7 +564,8 @@ class Context:
             return int(item)
 
         failed = []
-        f, k = FETCH_STAGED_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None))
+        f, k = FETCH_STAGED_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None,
+                                                                                     self if topk else None))
         st = StreamStats()
         rc = lib().qasr_run_stream_staged(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
         if failed:

@@ -15,7 +15,8 @@ in the process group's TCPStore (store.add per utterance, longest first), each
 rank's continuous-batching stream pulling the next utterance whenever a slot
 frees; run_shard -- the static longest-first split in fixed batches.
 Token log-probabilities (context option token_logprobs, run_stream's
-logprobs=True) are not gathered across ranks here: only token ids are.
+logprobs=True) and top-K alternatives (option top_k, topk=True) are not
+gathered across ranks here: only token ids are.
 """
 from __future__ import annotations
 
