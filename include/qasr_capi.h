@@ -426,6 +426,91 @@ int qasr_write_synthetic_gguf(const char *path, const char *config, uint64_t see
  * given (config, seed, wtype) changes, so a cached synthetic model is keyed on it */
 int qasr_synthetic_gguf_version(void);
 
+/* ---- test only: one kernel launcher on caller-supplied arrays --------------- */
+/* (csrc/kernel_harness.hip; tests/kernel_util.py holds the bindings.)  Every
+ * pointer is a host pointer; a null input is not passed on, a null output is not
+ * allocated.  Per call: each input is uploaded with `guard` extra rows after its
+ * last row filled with 0xFF bytes (fp16 / fp32 NaN; 0x7F for int8 quants); each
+ * output is allocated with `guard` rows before and after its rows, every byte
+ * pre-filled with 0xFF, and copied back whole ((rows + 2 * guard) * ld elements)
+ * after the launch.  The launch goes on the null stream and is synchronised.
+ * Returns QASR_OK with `declined` = 1 and `msg` set where the launcher took no
+ * kernel (a false return or a take_declined message), QASR_ERR_DEVICE on a HIP
+ * error; `tag` names the kernel that ran (kernels.h note_kernel). */
+typedef struct {
+    int32_t launcher;        /* 0 launch_gemm (AM_DENSE), 1 launch_gemm_q8, 2 launch_gemm_skinny, 3 launch_gemm_skinny_q8 */
+    int32_t epi;             /* GemmEpi */
+    int32_t M, N, K;
+    int32_t lda, ldw, ldad, ldr, ldo, ldo16, ldoq;
+    int32_t regs_staged, n_valid, skinny_inflight, wdef;
+    int32_t guard;
+    int32_t pe_rows;         /* rows of pe [pe_rows][N] */
+    const uint16_t *A;       /* fp16 [M][lda] */
+    const uint16_t *W;       /* fp16 [N][ldw] */
+    const int8_t *Aq;        /* int8 [M][lda] */
+    const float *Ad;         /* [M][ldad] */
+    const int8_t *Wq;        /* int8 [N][ldw] */
+    const uint16_t *Wd;      /* fp16 [N][K / 32] */
+    const float *bias;       /* [N] */
+    const float *res;        /* [M][ldr] */
+    const float *pe;
+    const int32_t *pe_pos;   /* [M] */
+    float *out_f32;          /* [M + 2 guard][ldo] */
+    uint16_t *out_f16;       /* [M + 2 guard][ldo16] */
+    int8_t *out_q;           /* [M + 2 guard][ldoq] */
+    float *out_d;            /* [M + 2 guard][ldoq / 32] */
+    uint64_t *amax;          /* [M + 2 guard] packed argmax keys (rows zero before the launch) */
+    uint16_t *gelu_out;      /* [65536]: the engine's GELU table as the launch used it */
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_gemm_args;
+int qasr_kt_gemm(int device, qasr_kt_gemm_args *a);
+
+typedef struct {
+    int32_t epi;             /* GemmEpi */
+    int32_t M, N, K;         /* N = output columns */
+    int32_t wrows;           /* weight rows: N, or 2 N for the SwiGLU epilogues */
+    int32_t ldx, ldxh, ldr, ldo, ldo16;
+    int32_t embd_rows, hist_stride;
+    int32_t guard;
+    int32_t launches;        /* >= 1: the same launch repeated on the same device state */
+    float eps;
+    const float *x;          /* fp32 [M][ldx] */
+    const uint16_t *xh;      /* fp16 [M][ldxh] */
+    const float *norm_w;     /* [K] */
+    const uint16_t *W;       /* fp16 [wrows][K] */
+    const int8_t *Wq;        /* int8 [wrows][K], with Wd */
+    const uint16_t *Wd;      /* fp16 [wrows][K / 32] */
+    const float *bias;       /* [N] */
+    const float *res;        /* [M][ldr] */
+    const int32_t *embd_ids; /* [M] */
+    const uint16_t *embd;    /* fp16 [embd_rows][K] */
+    float *x_store;          /* [M + 2 guard][ldx] */
+    float *out_f32;          /* [M + 2 guard][ldo] */
+    uint16_t *out_f16;       /* [M + 2 guard][ldo16] */
+    uint64_t *amax;          /* [8] in (zero at rest) / out */
+    /* EPI_ARGMAX bookkeeping group: all or none; in / out */
+    uint32_t *done;          /* [1] */
+    int32_t *tok_out;        /* [8] */
+    int32_t *hist;           /* [M][hist_stride] */
+    int32_t *step;           /* [1] */
+    int32_t *pos;            /* [8] */
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_gemv_args;
+int qasr_kt_gemv(int device, qasr_kt_gemv_args *a);
+
+typedef struct {
+    int32_t M, K, ldx, gather_C, guard;
+    const float *x32;        /* one of x32 / x16: [M][ldx] */
+    const uint16_t *x16;
+    int8_t *q;               /* [M + 2 guard][K] */
+    float *d;                /* [M + 2 guard][K / 32] */
+} qasr_kt_quant_args;
+int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,12 +315,14 @@ __global__ __launch_bounds__(128 * WNW) void gemm_glds_kernel(GemmArgs g) {
 template <int BM, int BN, int KS, int AMODE, int EPI>
 static void run_gemm(const GemmArgs &g, hipStream_t s) {
     dim3 grid(g.N / BN, (g.M + BM - 1) / BM);
+    note_kernel("gemm", 3, BM, BN, KS);
     hipLaunchKernelGGL((gemm_kernel<BM, BN, KS, AMODE, EPI>), grid, dim3(256), 0, s, g);
 }
 
 template <int BM, int BN, int KS, int NB, int AMODE, int EPI, int WNW = 2>
 static void run_glds(const GemmArgs &g, hipStream_t s) {
     dim3 grid(g.N / BN, (g.M + BM - 1) / BM);
+    note_kernel("glds", 5, BM, BN, KS, NB, WNW);
     hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, KS, NB, AMODE, EPI, WNW>), grid, dim3(128 * WNW), 0, s, g);
 }
 
@@ -364,6 +366,8 @@ static void dispatch_tiles(const GemmArgs &g, hipStream_t s) {
         // prefill qkv 370 -> 280, o 167 -> 125, gate/up 510 -> 351, down 220 -> 166,
         // encoder fc1 383 -> 258, fc2 251 -> 176, qkv 219 -> 164
         const bool big = g.M >= 2048 && g.N % 128 == 0;
+        // 16-byte operand loads; no tile reads a partial 32-deep slab
+        if (g.K % 32 != 0 || g.lda % 8 != 0 || g.ldw % 8 != 0) return note_declined_shape("launch_gemm", g.M, g.N, g.K);
         if constexpr (EPI != EPI_ARGMAX) {
             if (g.M >= 2048 && g.N >= 256 && g.N % 32 == 0 && g.K % 128 == 0 && g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldo % 4 == 0 &&
                 g.ldo16 % 4 == 0 && (!g.res || g.ldr % 4 == 0) && !g.regs_staged) {
@@ -371,6 +375,8 @@ static void dispatch_tiles(const GemmArgs &g, hipStream_t s) {
                 return;
             }
         }
+        // every tile below is 64 columns or a multiple wide (grid.x = N / BN)
+        if (g.N % 64 != 0) return note_declined_shape("launch_gemm", g.M, g.N, g.K);
         if (big && !g.regs_staged && g.N % 256 == 0) {
             run_glds<256, 256, 1, 3, AMODE, EPI, 4>(g, s);
         } else if (big && !g.regs_staged) {   // LDS-DMA stages (tools/micro/glds_gemm_bench.hip: +5-10 %)
@@ -415,10 +421,29 @@ void note_declined(const char *what, int mode, int epi) {
     if (t_declined.empty())
         t_declined = std::string(what) + " has no kernel for mode " + std::to_string(mode) + " / epilogue " + std::to_string(epi);
 }
+void note_declined_shape(const char *what, int M, int N, int K) {
+    if (t_declined.empty())
+        t_declined = std::string(what) + " has no kernel for shape " + std::to_string(M) + " x " + std::to_string(N) + " x " +
+                     std::to_string(K) + " with these leading dimensions (kernels.h)";
+}
 bool take_declined(std::string *msg) {
     if (t_declined.empty()) return false;
     if (msg) *msg = t_declined;
     t_declined.clear();
+    return true;
+}
+
+// the last launch's kernel, kept as its parts (formatted only when asked for)
+static thread_local struct { const char *family; int n, p[5]; } t_kernel = {nullptr, 0, {0, 0, 0, 0, 0}};
+void note_kernel(const char *family, int n, int a, int b, int c, int d, int e) { t_kernel = {family, n, {a, b, c, d, e}}; }
+bool take_kernel(std::string *tag) {
+    if (!t_kernel.family) return false;
+    if (tag) {
+        *tag = t_kernel.family;
+        for (int i = 0; i < t_kernel.n; i++) *tag += (i ? "," : "<") + std::to_string(t_kernel.p[i]);
+        if (t_kernel.n) *tag += ">";
+    }
+    t_kernel.family = nullptr;
     return true;
 }
 
@@ -467,7 +492,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs g) {
     // ---- prologue: x rows -> fp16 in LDS (optionally RMS-normalised); each
     //      thread owns 4 consecutive elements per 1024-wide pass, one vector load each
     constexpr int KP = (NK * 512 + 1023) / 1024;
-    if (g.norm_w || g.x) {
+    if (g.norm_w || g.x || g.embd_ids) {   // (a gathered row is an fp32 row: without this, embd_ids alone read the null xh)
         float xr[MR][KP][4];
         double ss[MR];
 #pragma unroll
@@ -826,6 +851,7 @@ static void run_gemv_q8(const GemvArgs &g, hipStream_t s) {
     int blocks = (g.N + per_block - 1) / per_block;
     if (blocks > 1024) blocks = 1024;
     const size_t lds = (size_t)MR * g.K + (size_t)MR * (g.K / 32) * 4;
+    note_kernel("gemv_q8", 3, CPW, MR, NK);
     hipLaunchKernelGGL((gemv_q8_kernel<EPI, CPW, MR, NK>), dim3(blocks), dim3(256), lds, s, g);
 }
 
@@ -859,6 +885,7 @@ static void run_gemv(const GemvArgs &g, hipStream_t s) {
     int blocks = (g.N + per_block - 1) / per_block;
     if (blocks > 1024) blocks = 1024;   // 256 CUs x 4 resident workgroups, grid-stride beyond
     const size_t lds = (size_t)MR * g.K * 2;
+    note_kernel("gemv", 3, CPW, MR, NK);
     hipLaunchKernelGGL((gemv_kernel<EPI, CPW, MR, NK>), dim3(blocks), dim3(256), lds, s, g);
 }
 
@@ -891,7 +918,12 @@ static void gemv_mr(const GemvArgs &g, hipStream_t s) {
 void launch_gemv(int epi, const GemvArgs &g, hipStream_t s) {
     if (g.M <= 0) return;
     if (launch_gemv1(epi, g, s)) return;
+    // SwiGLU reads whole 16-row gate / up groups of W
+    const bool swiglu = epi == EPI_SWIGLU_F16 || epi == EPI_SWIGLU_F32;
+    if (g.M > 8 || (swiglu && g.N % 16 != 0)) return note_declined_shape("launch_gemv", g.M, g.N, g.K);
     if (g.Wd) {   // Q8_0 weights: fp32 x only
+        // whole 32-blocks, at most 8 sweeps of 1024
+        if (g.K % 32 != 0 || g.K > 8192 || g.ldx % 4 != 0) return note_declined_shape("launch_gemv (Q8_0)", g.M, g.N, g.K);
         switch (epi) {
             case EPI_F32: gemv_q8_mr<EPI_F32>(g, s); break;
             case EPI_SWIGLU_F32: gemv_q8_mr<EPI_SWIGLU_F32>(g, s); break;
@@ -899,6 +931,10 @@ void launch_gemv(int epi, const GemvArgs &g, hipStream_t s) {
         }
         return;
     }
+    // 16-byte pieces of a row, at most 8 sweeps of 512 (a longer row would be summed short)
+    const bool f32x = g.norm_w || g.x || g.embd_ids;   // the kernel's fp32 prologue (x, or the gathered rows and x_store), else xh
+    if (g.K % 8 != 0 || g.K > 4096 || (f32x ? g.ldx % 4 != 0 : g.ldxh % 8 != 0))
+        return note_declined_shape("launch_gemv", g.M, g.N, g.K);
     switch (epi) {
         case EPI_F32: gemv_mr<EPI_F32>(g, s); break;
         case EPI_SWIGLU_F16: gemv_mr<EPI_SWIGLU_F16>(g, s); break;

@@ -457,6 +457,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs g) {
 template <int EPI, int AMODE = AM_DENSE>
 static inline void run_gemm8p(const GemmArgs &g, hipStream_t s) {
     const int tiles = ((g.N + 255) / 256) * ((g.M + 255) / 256);
+    note_kernel("gemm8p", 0);
     hipLaunchKernelGGL((gemm8p_kernel<EPI, AMODE>), dim3(tiles), dim3(512), 0, s, g);
 }
 

@@ -133,6 +133,7 @@ __global__ __launch_bounds__(256) void gemm_q8_kernel(GemmArgs g) {
 template <int BM, int BN, int KS, int EPI>
 static void run_gemm_q8(const GemmArgs &g, hipStream_t s) {
     dim3 grid(g.N / BN, (g.M + BM - 1) / BM);
+    note_kernel("gemm_q8", 3, BM, BN, KS);
     hipLaunchKernelGGL((gemm_q8_kernel<BM, BN, KS, EPI>), grid, dim3(256), 0, s, g);
 }
 
@@ -147,8 +148,7 @@ static void dispatch_q8(const GemmArgs &g, hipStream_t s) {
         // encode 80.6 -> 64.3 (64 x 64: 130.3 / 67.4, 64 x 128: 122.5 / 65.2;
         // 128 x 128 with 128-wide K stages: 306 ms, one workgroup a CU)
         // (128 x 64 with 128-wide K stages: 162.1 ms; 96 x 64: 129.7)
-        if (big && g.N % 64 == 0) run_gemm_q8<128, 64, 2, EPI>(g, s);
-        else if (big) run_gemm_q8<128, 128, 2, EPI>(g, s);
+        if (big) run_gemm_q8<128, 64, 2, EPI>(g, s);
         else run_gemm_q8<64, 64, 4, EPI>(g, s);
     } else {
         run_gemm_q8<64, 64, 1, EPI>(g, s);
@@ -157,11 +157,13 @@ static void dispatch_q8(const GemmArgs &g, hipStream_t s) {
 
 void launch_gemm_q8(int epi, const GemmArgs &g, hipStream_t s) {
     if (g.M <= 0) return;
+    // 64-column tiles of whole 32-blocks, 16-byte int8 loads
+    if (g.N % 64 != 0 || g.K % 32 != 0 || g.lda % 16 != 0 || g.ldw % 16 != 0) return note_declined_shape("launch_gemm_q8", g.M, g.N, g.K);
     switch (epi) {
         case EPI_F32: dispatch_q8<EPI_F32>(g, s); break;
         case EPI_GELU_F16: dispatch_q8<EPI_GELU_F16>(g, s); break;
         case EPI_SWIGLU_F32: dispatch_q8<EPI_SWIGLU_F32>(g, s); break;
-        default: break;
+        default: note_declined("launch_gemm_q8", 0, epi); break;
     }
 }
 

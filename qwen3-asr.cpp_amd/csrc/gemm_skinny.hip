@@ -520,6 +520,7 @@ static void run_skinny_v(const GemmArgs &g, hipStream_t s) {
     const int cpw = (g.K >> 7) % KW == 0 && g.skinny_inflight ? (g.K >> 7) / KW : 0;   // whole chunks a wave: all in flight
     // (a CPW form is instantiated only where its chunk images fit the LDS: <= 128 KiB)
     constexpr int CH = KW * MT * 16 * 128 * 2;
+    note_kernel("skinny", 5, MT, NT, KW, VAR, cpw == 1 || (cpw == 2 && 2 * CH <= 131072) || (cpw == 3 && 3 * CH <= 131072) ? cpw : 0);
     if (cpw == 1) hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, EPI, VAR, 1>), grid, dim3(64 * KW), 0, s, g);
     else if (cpw == 2 && 2 * CH <= 131072) hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, EPI, VAR, 2 * CH <= 131072 ? 2 : 1>), grid, dim3(64 * KW), 0, s, g);
     else if (cpw == 3 && 3 * CH <= 131072) hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, EPI, VAR, 3 * CH <= 131072 ? 3 : 1>), grid, dim3(64 * KW), 0, s, g);
@@ -527,9 +528,11 @@ static void run_skinny_v(const GemmArgs &g, hipStream_t s) {
 }
 template <int MT, int NT, int KW, int EPI>
 static void run_skinny(const GemmArgs &g, hipStream_t s) {
-    if (g.regs_staged) hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, EPI, 0>), dim3(g.N / (16 * NT), (g.M + 16 * MT - 1) / (16 * MT)),
-                                          dim3(64 * KW), 0, s, g);
-    else if (g.wdef) run_skinny_v<MT, NT, KW, EPI, 4 | 8>(g, s);
+    if (g.regs_staged) {
+        note_kernel("skinny", 5, MT, NT, KW, 0, 0);
+        hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, EPI, 0>), dim3(g.N / (16 * NT), (g.M + 16 * MT - 1) / (16 * MT)),
+                           dim3(64 * KW), 0, s, g);
+    } else if (g.wdef) run_skinny_v<MT, NT, KW, EPI, 4 | 8>(g, s);
     else run_skinny_v<MT, NT, KW, EPI, 4>(g, s);
 }
 
@@ -538,6 +541,8 @@ static void run_skinny_q8(const GemmArgs &g, hipStream_t s) {
     dim3 grid(g.N / (16 * NT), (g.M + 16 * MT - 1) / (16 * MT));
     const int cpw = (g.K >> 7) % KW == 0 && g.skinny_inflight ? (g.K >> 7) / KW : 0;
     constexpr int CH = KW * MT * 16 * 128;
+    const bool inf = cpw == 1 || (cpw == 2 && 2 * CH <= 131072) || (cpw == 3 && 3 * CH <= 131072);
+    note_kernel("skinny_q8", 5, MT, NT, KW, g.regs_staged ? 0 : 4, !g.regs_staged && inf ? cpw : 0);
     if (g.regs_staged) hipLaunchKernelGGL((gemm_skinny_q8_kernel<MT, NT, KW, EPI, 0>), grid, dim3(64 * KW), 0, s, g);
     else if (cpw == 1) hipLaunchKernelGGL((gemm_skinny_q8_kernel<MT, NT, KW, EPI, 4, 1>), grid, dim3(64 * KW), 0, s, g);
     else if (cpw == 2 && 2 * CH <= 131072) hipLaunchKernelGGL((gemm_skinny_q8_kernel<MT, NT, KW, EPI, 4, 2 * CH <= 131072 ? 2 : 1>), grid, dim3(64 * KW), 0, s, g);
@@ -631,7 +636,11 @@ bool launch_gemm_skinny_q8(int epi, const GemmArgs &g, hipStream_t s) {
             return true;
         case EPI_SWIGLU_F32:
             if (g.N % 32 != 0) return false;
-            skinny_q8_mt<2, 2, 4, EPI_SWIGLU_F32>(g, s);
+            // K over 8 waves, as EPI_SWIGLU_Q8 below: a value's chunks go to the same waves and the partial
+            // sums add up in the same order, so that epilogue quantises exactly these bits (kernels.h; over
+            // 4 waves one quant in ~50,000 came out one apart, tests/test_gpu_kernels.py test_skinny_swiglu).
+            // The decode step takes this form only where EPI_SWIGLU_Q8 declines.
+            skinny_q8_mt<2, 2, 8, EPI_SWIGLU_F32>(g, s);
             return true;
         case EPI_SWIGLU_Q8:
             // 64-column blocks: 32 output columns, one Q8_0 block a row; K over 8 waves

@@ -142,6 +142,7 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs g) {
 template <int EPI, int K, int RPW>
 static void run_gemv1(const GemvArgs &g, hipStream_t s) {
     const int grid = (g.N + 4 * RPW - 1) / (4 * RPW);
+    note_kernel("gemv1", 2, K, RPW);
     hipLaunchKernelGGL((gemv1_kernel<EPI, K, RPW>), dim3(grid), dim3(256), 0, s, g);
 }
 

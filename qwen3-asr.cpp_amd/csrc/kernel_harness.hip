@@ -1,0 +1,227 @@
+// kernel_harness.hip -- test-only C entry points (include/qasr_capi.h, "test
+// only"): one GEMM / GEMV / quantisation launcher of kernels.h on arrays the
+// caller supplies, so tests/test_gpu_kernels.py can hold every tile, tiling and
+// epilogue to a float64 reference without a model.
+//
+// What a kernel may not touch is made visible: inputs carry `guard` rows of
+// 0xFF bytes (NaN) after their last row (0x7F for int8 quants), outputs are
+// allocated with `guard` rows on both sides and every byte 0xFF before the
+// launch, and come back whole.  A launcher that takes no kernel is reported
+// as declined, never as success.
+#include "engine_impl.h"
+
+using namespace qasr;
+using qasr::eng::fail;
+
+namespace {
+
+struct KtBuf {
+    char *d = nullptr;
+    size_t bytes = 0, off = 0;   // off: byte offset of the first real row
+    ~KtBuf() {
+        if (d) (void)hipFree(d);
+    }
+    template <class T>
+    T *ptr() const { return d ? (T *)(d + off) : nullptr; }
+};
+
+// input: rows x ld elements of esz bytes from host, then guard rows of `fill` bytes
+int put_in(KtBuf &b, const void *host, long rows, long ld, int esz, int guard, int fill) {
+    if (!host) return 0;
+    const size_t real = (size_t)rows * ld * esz;
+    b.bytes = real + (size_t)guard * ld * esz + 256;
+    HIPCHK(hipMalloc((void **)&b.d, b.bytes));
+    HIPCHK(hipMemset(b.d, fill, b.bytes));
+    if (real) HIPCHK(hipMemcpy(b.d, host, real, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// output: guard + rows + guard rows of ld elements, every byte 0xFF
+int put_out(KtBuf &b, const void *host, long rows, long ld, int esz, int guard) {
+    if (!host) return 0;
+    b.bytes = (size_t)(rows + 2 * guard) * ld * esz;
+    b.off = (size_t)guard * ld * esz;
+    HIPCHK(hipMalloc((void **)&b.d, b.bytes));
+    HIPCHK(hipMemset(b.d, 0xFF, b.bytes));
+    return 0;
+}
+
+// in / out state (no guards): host -> device
+int put_state(KtBuf &b, const void *host, size_t bytes) {
+    if (!host) return 0;
+    b.bytes = bytes;
+    HIPCHK(hipMalloc((void **)&b.d, bytes));
+    HIPCHK(hipMemcpy(b.d, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int get(const KtBuf &b, void *host) {
+    if (b.d && host) HIPCHK(hipMemcpy(host, b.d, b.bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+void copy_str(char *dst, size_t cap, const std::string &s) {
+    const size_t n = std::min(cap - 1, s.size());
+    memcpy(dst, s.data(), n);
+    dst[n] = 0;
+}
+
+// after the launch(es): synchronise, collect the tag and any declined message
+template <class Args>
+int finish(Args *a, bool ran) {
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipDeviceSynchronize();
+    std::string msg, tag;
+    const bool declined = take_declined(&msg);
+    const bool tagged = take_kernel(&tag);
+    if (le != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (se != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel run: ") + hipGetErrorString(se));
+    a->declined = declined || !ran;
+    if (a->declined && msg.empty()) msg = "the launcher returned false";
+    if (!a->declined && !tagged) return fail(QASR_ERR_STATE, "the launcher recorded no kernel tag");
+    copy_str(a->tag, sizeof a->tag, a->declined ? std::string() : tag);
+    copy_str(a->msg, sizeof a->msg, msg);
+    return 0;
+}
+
+int use_device(int device) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return fail(QASR_ERR_DEVICE, "no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    (void)take_declined(nullptr);
+    (void)take_kernel(nullptr);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int qasr_kt_gemm(int device, qasr_kt_gemm_args *a) {
+    if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launcher < 0 || a->launcher > 3)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const bool q8 = a->launcher == 1 || a->launcher == 3;
+    if (q8 ? !(a->Aq && a->Ad && a->Wq && a->Wd) : !(a->A && a->W)) return fail(QASR_ERR_ARG, "operands missing");
+    if (a->lda < a->K || a->ldw < a->K || (q8 && a->ldad < a->K / 32) || (a->pe && (!a->pe_pos || a->pe_rows <= 0)))
+        return fail(QASR_ERR_ARG, "leading dimensions smaller than the rows");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int M = a->M, N = a->N, K = a->K, G = a->guard;
+    KtBuf A, W, Aq, Ad, Wq, Wd, bias, res, pe, pe_pos, gelu, o32, o16, oq, od, amax;
+    if ((rc = put_in(A, a->A, M, a->lda, 2, G, 0xFF)) || (rc = put_in(W, a->W, N, a->ldw, 2, G, 0xFF)) ||
+        (rc = put_in(Aq, a->Aq, M, a->lda, 1, G, 0x7F)) || (rc = put_in(Ad, a->Ad, M, a->ldad, 4, G, 0xFF)) ||
+        (rc = put_in(Wq, a->Wq, N, a->ldw, 1, G, 0x7F)) || (rc = put_in(Wd, a->Wd, N, K / 32, 2, G, 0xFF)) ||
+        (rc = put_in(bias, a->bias, 1, N, 4, 1, 0xFF)) || (rc = put_in(res, a->res, M, a->ldr, 4, G, 0xFF)) ||
+        (rc = put_in(pe, a->pe, a->pe_rows, N, 4, 1, 0xFF)) || (rc = put_in(pe_pos, a->pe_pos, 1, M, 4, 0, 0)) ||
+        (rc = put_out(o32, a->out_f32, M, a->ldo, 4, G)) || (rc = put_out(o16, a->out_f16, M, a->ldo16, 2, G)) ||
+        (rc = put_out(oq, a->out_q, M, a->ldoq, 1, G)) || (rc = put_out(od, a->out_d, M, a->ldoq / 32, 4, G)) ||
+        (rc = put_out(amax, a->amax, M, 1, 8, G)))
+        return rc;
+    if (amax.d) HIPCHK(hipMemset(amax.ptr<char>(), 0, (size_t)M * 8));
+    std::vector<uint16_t> lut;
+    gelu_table(lut);
+    if ((rc = put_in(gelu, lut.data(), 1, 65536, 2, 0, 0))) return rc;
+    if (a->gelu_out) memcpy(a->gelu_out, lut.data(), 65536 * 2);
+
+    GemmArgs g{};
+    g.A = A.ptr<uint16_t>(); g.lda = a->lda;
+    g.W = W.ptr<uint16_t>(); g.ldw = a->ldw;
+    g.M = M; g.N = N; g.K = K;
+    g.bias = bias.ptr<float>();
+    g.res = res.ptr<float>(); g.ldr = a->ldr;
+    g.out_f32 = o32.ptr<float>(); g.ldo = a->ldo;
+    g.out_f16 = o16.ptr<uint16_t>(); g.ldo16 = a->ldo16;
+    g.gelu = gelu.ptr<uint16_t>();
+    g.pe = pe.ptr<float>(); g.pe_pos = pe_pos.ptr<int>();
+    g.amax = amax.ptr<unsigned long long>();
+    g.n_valid = a->n_valid;
+    g.Aq = Aq.ptr<int8_t>(); g.Ad = Ad.ptr<float>(); g.ldad = a->ldad;
+    g.Wq = Wq.ptr<int8_t>(); g.Wd = Wd.ptr<uint16_t>();
+    g.regs_staged = a->regs_staged;
+    g.skinny_inflight = a->skinny_inflight;
+    g.out_q = oq.ptr<int8_t>(); g.out_d = od.ptr<float>(); g.ldoq = a->ldoq;
+    g.wdef = a->wdef;
+
+    bool ran = true;
+    switch (a->launcher) {
+        case 0: launch_gemm(AM_DENSE, a->epi, g, nullptr); break;
+        case 1: launch_gemm_q8(a->epi, g, nullptr); break;
+        case 2: ran = launch_gemm_skinny(a->epi, g, nullptr); break;
+        default: ran = launch_gemm_skinny_q8(a->epi, g, nullptr); break;
+    }
+    if ((rc = finish(a, ran))) return rc;
+    if ((rc = get(o32, a->out_f32)) || (rc = get(o16, a->out_f16)) || (rc = get(oq, a->out_q)) || (rc = get(od, a->out_d)) ||
+        (rc = get(amax, a->amax)))
+        return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) {
+    if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || a->wrows < a->N)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    if (!(a->Wq ? a->Wd != nullptr : a->W != nullptr) || !(a->x || a->xh || (a->embd_ids && a->embd)))
+        return fail(QASR_ERR_ARG, "operands missing");
+    const bool book = a->done || a->tok_out || a->hist || a->step || a->pos;
+    if (book && !(a->done && a->tok_out && a->hist && a->step && a->pos && a->amax && a->hist_stride > 0))
+        return fail(QASR_ERR_ARG, "the bookkeeping group is all or none");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int M = a->M, N = a->N, K = a->K, G = a->guard;
+    KtBuf x, xh, nw, W, Wq, Wd, bias, res, ids, embd, xs, o32, o16, amax, done, tok, hist, step, pos;
+    if ((rc = put_in(x, a->x, M, a->ldx, 4, G, 0xFF)) || (rc = put_in(xh, a->xh, M, a->ldxh, 2, G, 0xFF)) ||
+        (rc = put_in(nw, a->norm_w, 1, K, 4, 1, 0xFF)) || (rc = put_in(W, a->W, a->wrows, K, 2, G, 0xFF)) ||
+        (rc = put_in(Wq, a->Wq, a->wrows, K, 1, G, 0x7F)) || (rc = put_in(Wd, a->Wd, a->wrows, K / 32, 2, G, 0xFF)) ||
+        (rc = put_in(bias, a->bias, 1, N, 4, 1, 0xFF)) || (rc = put_in(res, a->res, M, a->ldr, 4, G, 0xFF)) ||
+        (rc = put_in(ids, a->embd_ids, 1, M, 4, 0, 0)) || (rc = put_in(embd, a->embd, a->embd_rows, K, 2, G, 0xFF)) ||
+        (rc = put_out(xs, a->x_store, M, a->ldx, 4, G)) || (rc = put_out(o32, a->out_f32, M, a->ldo, 4, G)) ||
+        (rc = put_out(o16, a->out_f16, M, a->ldo16, 2, G)) || (rc = put_state(amax, a->amax, 8 * 8)) ||
+        (rc = put_state(done, a->done, 4)) || (rc = put_state(tok, a->tok_out, 8 * 4)) ||
+        (rc = put_state(hist, a->hist, (size_t)M * a->hist_stride * 4)) || (rc = put_state(step, a->step, 4)) ||
+        (rc = put_state(pos, a->pos, 8 * 4)))
+        return rc;
+
+    GemvArgs g{};
+    g.x = x.ptr<float>(); g.ldx = a->ldx;
+    g.xh = xh.ptr<uint16_t>(); g.ldxh = a->ldxh;
+    g.norm_w = nw.ptr<float>(); g.eps = a->eps;
+    g.W = a->Wq ? (const uint16_t *)Wq.ptr<int8_t>() : W.ptr<uint16_t>();
+    g.K = K; g.N = N; g.M = M;
+    g.Wd = Wd.ptr<uint16_t>();
+    g.bias = bias.ptr<float>();
+    g.res = res.ptr<float>(); g.ldr = a->ldr;
+    g.out_f32 = o32.ptr<float>(); g.ldo = a->ldo;
+    g.out_f16 = o16.ptr<uint16_t>(); g.ldo16 = a->ldo16;
+    g.amax = amax.ptr<unsigned long long>();
+    g.embd_ids = ids.ptr<int32_t>(); g.embd = embd.ptr<uint16_t>(); g.x_store = xs.ptr<float>();
+    g.done = done.ptr<unsigned int>(); g.tok_out = tok.ptr<int32_t>(); g.hist = hist.ptr<int32_t>();
+    g.hist_stride = a->hist_stride; g.step = step.ptr<int>(); g.pos = pos.ptr<int>();
+
+    for (int i = 0; i < a->launches; i++) {
+        launch_gemv(a->epi, g, nullptr);
+        if (i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
+    }
+    if ((rc = finish(a, true))) return rc;
+    if ((rc = get(xs, a->x_store)) || (rc = get(o32, a->out_f32)) || (rc = get(o16, a->out_f16)) || (rc = get(amax, a->amax)) ||
+        (rc = get(done, a->done)) || (rc = get(tok, a->tok_out)) || (rc = get(hist, a->hist)) || (rc = get(step, a->step)) ||
+        (rc = get(pos, a->pos)))
+        return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a) {
+    if (!a || a->M <= 0 || a->K <= 0 || a->K % 32 != 0 || a->guard < 0 || !a->q || !a->d || !a->x32 == !a->x16 || a->gather_C < 0)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    // the widest column a row reads: K - 1, or (15, K / 16 - 1) of the gathered [h][c] order
+    const long last = a->gather_C > 0 ? 15L * a->gather_C + (a->K / 16 - 1) : a->K - 1;
+    if (a->ldx <= last) return fail(QASR_ERR_ARG, "ldx smaller than the rows read");
+    int rc = use_device(device);
+    if (rc) return rc;
+    KtBuf x32, x16, q, d;
+    if ((rc = put_in(x32, a->x32, a->M, a->ldx, 4, a->guard, 0xFF)) || (rc = put_in(x16, a->x16, a->M, a->ldx, 2, a->guard, 0xFF)) ||
+        (rc = put_out(q, a->q, a->M, a->K, 1, a->guard)) || (rc = put_out(d, a->d, a->M, a->K / 32, 4, a->guard)))
+        return rc;
+    launch_quantize_q8(x32.ptr<float>(), x16.ptr<uint16_t>(), a->ldx, a->M, a->K, a->gather_C, q.ptr<int8_t>(), d.ptr<float>(), nullptr);
+    const hipError_t le = hipGetLastError(), se = hipDeviceSynchronize();
+    if (le != hipSuccess || se != hipSuccess)
+        return fail(QASR_ERR_DEVICE, std::string("launch_quantize_q8: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    if ((rc = get(q, a->q)) || (rc = get(d, a->d))) return rc;
+    return 0;
+}

@@ -53,7 +53,8 @@ enum GemmEpi {
     EPI_F16 = 4,        // out_f16 = acc (+bias)
     EPI_SWIGLU_F32 = 5, // as EPI_SWIGLU_F16 with fp32 out_f32 (input of a Q8_0 layer)
     EPI_SWIGLU_Q8 = 6,  // as EPI_SWIGLU_F32, quantised to Q8_0 in the epilogue: out_q / out_d
-                        // (the bits of EPI_SWIGLU_F32 + launch_quantize_q8); skinny Q8_0 GEMM only
+                        // (the bits of EPI_SWIGLU_F32 + launch_quantize_q8: launch_gemm_skinny_q8 splits K over
+                        // the same 8 waves for both); skinny Q8_0 GEMM only
 };
 enum GemmAMode {
     AM_DENSE = 0,       // A [M][lda] fp16 row-major
@@ -86,12 +87,33 @@ struct GemmArgs {
     int8_t *out_q; float *out_d; int ldoq;   // EPI_SWIGLU_Q8: int8 [M][ldoq], fp32 block scales [M][ldoq / 32]
     int wdef;                             // skinny GEMMs: weights with the default cache policy (1) or nontemporal (0)
 };
+// Shapes the launchers take (anything else is declined, see below -- never a
+// partial computation):
+//   launch_gemm, AM_DENSE   N % 64 == 0, K % 32 == 0, lda % 8 == 0, ldw % 8 == 0
+//                           (the 8-phase tile of >= 2048 rows: N >= 256, N % 32 == 0, K % 128 == 0,
+//                           ldo / ldo16 / ldr % 4 == 0); SwiGLU: N weight rows give N / 2 columns
+//   launch_gemm_q8          N % 64 == 0, K % 32 == 0, lda % 16 == 0, ldw % 16 == 0 (int8 elements);
+//                           scales Ad [M][ldad], Wd [N][K / 32]
+//   launch_gemm_skinny      1 <= M <= 128, K % 128 == 0, lda % 8 == 0, ldw % 8 == 0; N % 16 == 0
+//                           (SwiGLU: N % 32, argmax: N % 64)            -- returns false otherwise
+//   launch_gemm_skinny_q8   1 <= M <= 128, K % 128 == 0, lda % 16 == 0, ldw % 16 == 0, ldad % 4 == 0;
+//                           N % 16 == 0 (SWIGLU_F32: N % 32; SWIGLU_Q8: N % 64, ldoq % 32 == 0)
+//   launch_gemv, f16 W      1 <= M <= 8, K % 8 == 0, K <= 4096, ldx % 4 == 0 (x) or ldxh % 8 == 0 (xh);
+//                           W rows K apart; SwiGLU: N % 16 == 0 (whole 16-row gate / up groups)
+//   launch_gemv, Q8_0 W     1 <= M <= 8, K % 32 == 0, K <= 8192, ldx % 4 == 0; SwiGLU: N % 16 == 0
 void launch_gemm(int amode, int epi, const GemmArgs &g, hipStream_t s);
-// an unsupported (mode, epilogue) pair launches nothing and is recorded for the
-// calling host thread; take_declined returns (and clears) it -- the engine
-// fails the call with it (QASR_ERR_STATE) instead of running short
+// an unsupported (mode, epilogue) pair or shape launches nothing and is recorded
+// for the calling host thread; take_declined returns (and clears) it -- the
+// engine fails the call with it (QASR_ERR_STATE) instead of running short
 void note_declined(const char *what, int mode, int epi);
+void note_declined_shape(const char *what, int M, int N, int K);
 bool take_declined(std::string *msg);
+// the kernel the last launch of this host thread chose: family and template
+// parameters ("glds<256,256,1,3,4>"), one thread-local store a launch (not part
+// of a captured graph's replay); take_kernel returns and clears it.  The kernel
+// tests assert it, so a retuned dispatch table cannot silently drop a tile.
+void note_kernel(const char *family, int n, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0);
+bool take_kernel(std::string *tag);
 // decode-batch GEMM (gemm_skinny.hip): dense A, M <= 128, K % 128 == 0; returns
 // false (nothing launched) for shapes it does not take, or when g.no_skinny.
 bool launch_gemm_skinny(int epi, const GemmArgs &g, hipStream_t s);
