@@ -43,6 +43,11 @@
  *   qasr_get_step_topk, qasr_get_topk, qasr_stream_topk
  *       no reference counterpart: the K largest logits of every greedy step
  *       as (id, log-probability) pairs (context option "top_k")
+ *   qasr_kv_fork, qasr_get_beams, qasr_prefill_slots
+ *       no reference counterpart: beam search (context option "beam_width") --
+ *       the KV-cache fork that lets a cache slot continue another slot's
+ *       history, the hypotheses of the last beam run, and a prefill into
+ *       chosen cache slots
  *
  * Conventions (mirroring the reference's):
  *   - return value: 0 = OK, nonzero = error; message via qasr_last_error().
@@ -323,6 +328,50 @@ int qasr_get_step_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int K)
 int qasr_get_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, int max_tokens, int K);
 int qasr_stream_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int cap_tokens, int K);
 
+/* ---- beam search (no reference counterpart) --------------------------------- */
+/* Context option "beam_width" [QASR_BEAM_WIDTH], 0 .. QASR_BEAM_MAX, default 0 (a
+ * value outside the range is QASR_ERR_ARG); 0 and 1 are greedy decoding, exactly
+ * the path without the option.  With W >= 2, qasr_run / qasr_run_staged /
+ * qasr_transcribe_batch decode every clip by beam search of width W: B clips use
+ * decode rows b * W .. b * W + W - 1 (B * W > max_batch is QASR_ERR_ARG), a step
+ * keeps the W best continuations of a clip's rows by summed log-probability, a
+ * continuation that ends in EOS among the step's W best is set aside as finished
+ * (at most W; W finished end the clip), and at the end the finished and, when the
+ * token budget ran out first, the live hypotheses are ranked by sum / length
+ * (DESIGN.md "Beam search" gives the rule to the tie).  tokens / n_tokens return
+ * each clip's best hypothesis, a trailing EOS popped as in greedy runs.  The beam
+ * step and the cache fork run on the device inside the replayed step graph.  The
+ * run's internal top-K uses K = W; option "top_k" keeps its value.  While W >= 2:
+ * qasr_run_stream* and a run with a token callback set return QASR_ERR_STATE, and
+ * so do qasr_get_logprobs / qasr_get_topk after a beam run.  Aligner models ignore
+ * the option.
+ *
+ * qasr_get_beams: all hypotheses of clip `clip` of the last beam run, best first.
+ *   tokens / logprobs: [cap_hyp][max_tokens] (logprobs may be NULL)
+ *   n_tokens / sum_logprob / finished: [cap_hyp]
+ * Returns their number (1..W) or minus an error code.  A popped EOS is not in
+ * tokens but is counted in sum_logprob.
+ *
+ * qasr_kv_fork: rows are forked inside groups of `group` consecutive rows (1..8; B
+ * a multiple of group, B <= max_batch; parent[b] in the same group as b).  After
+ * the call, for every row b, positions [from[b], to[b]) of cache slot b -- K, V
+ * and V^T, every decoder layer and kv head -- hold what slot parent[b] held at
+ * those positions BEFORE the call.  Swaps, cycles and several rows sharing one
+ * parent are all valid.  Everything else is unchanged: positions outside the
+ * range, also inside a partly covered 8-key V^T block; the read-ahead slack of
+ * V^T; slots >= B.  parent[b] == b or from[b] >= to[b] is a no-op for that row.
+ * Stream-ordered on the context's stream.  Bad arguments: QASR_ERR_ARG.
+ *
+ * qasr_prefill_slots: qasr_prefill with sequence b's prompt written to KV-cache
+ * slot slots[b] (0 .. max_batch - 1); logits, argmax and the step's top-K stay
+ * indexed by b. */
+#define QASR_BEAM_MAX 8
+int qasr_kv_fork(qasr_ctx *c, const int *parent, const int *from, const int *to, int B, int group);
+int qasr_get_beams(qasr_ctx *c, int clip, int32_t *tokens, float *logprobs, int *n_tokens, float *sum_logprob, int *finished,
+                   int cap_hyp, int max_tokens);
+int qasr_prefill_slots(qasr_ctx *c, const int32_t *ids, const int *P, const float *feats, const int *audio_pos, const int *N,
+                       const int *slots, int B, float *logits_last, int32_t *argmax);
+
 /* Per-token callback (Qwen3ASR::set_progress_callback, src/qwen3_asr.cpp:255-291):
  * called synchronously on the caller's thread after every greedy token of
  * qasr_run / qasr_run_staged -- the prefill's token first (n_generated = 1) --
@@ -510,6 +559,37 @@ typedef struct {
     float *d;                /* [M + 2 guard][K / 32] */
 } qasr_kt_quant_args;
 int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a);
+
+/* kv_fork_kernel on caller-supplied caches: kc / vc [layers][slots + guard][n_kv_head][max_ctx][128] and
+ * vt [layers][slots + guard][n_kv_head][128 * vt_ctx] fp16, where vt_ctx = max_ctx rounded up to 64 plus 384
+ * and the last `guard` slots of every layer are guard slots the caller filled with 0xFF; in / out, whole */
+typedef struct {
+    int32_t layers, n_kv_head, max_ctx, slots, guard;
+    int32_t B, group, blocks;      /* blocks: 8-key blocks of the grid (0 = up to max_ctx) */
+    const int32_t *parent, *from, *to;   /* [B] */
+    uint16_t *kc, *vc, *vt;
+    int32_t declined;
+} qasr_kt_kv_fork_args;
+int qasr_kt_kv_fork(int device, qasr_kt_kv_fork_args *a);
+
+/* beam_select_kernel on caller-supplied state: G groups of W rows, every group at step t.  In: ids / lps
+ * [G * W][W] (at t = 0 the kernel reads row g for group g).  In / out: cum, the finished table (fin_*
+ * [G * W]), n_fin / done [G].  Out, each [1 + 2 guard][G * W] with the guard rows 0xFF: tok, parent, from, to
+ * and the history slot h_par / h_id / h_lp.  t_out [G]: the groups' step index after the launch. */
+typedef struct {
+    int32_t W, G, t, eos, guard;
+    const int32_t *ids;
+    const float *lps;
+    const int32_t *P;              /* [G] */
+    float *cum;
+    int32_t *fin_row, *fin_t;
+    float *fin_sum, *fin_lp;
+    int32_t *n_fin, *done, *t_out;
+    int32_t *tok, *parent, *from, *to, *h_par, *h_id;
+    float *h_lp;
+    int32_t declined;
+} qasr_kt_beam_select_args;
+int qasr_kt_beam_select(int device, qasr_kt_beam_select_args *a);
 
 #ifdef __cplusplus
 }

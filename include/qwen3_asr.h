@@ -32,6 +32,19 @@ struct transcribe_params {
     // MI355X addition (trailing, default off): also return every token's top_k (1..8) alternatives
     // (context option "top_k" of qasr_capi.h; no reference counterpart)
     int32_t top_k = 0;
+    // MI355X addition (trailing, default off): beam search of this width (2..8) instead of greedy decoding
+    // (context option "beam_width" of qasr_capi.h; no reference counterpart).  0 and 1 are greedy.  A beam run
+    // reports no per-token progress and fills neither token_logprobs nor alt_tokens: its values are in
+    // transcribe_result::beams
+    int32_t beam_width = 0;
+};
+
+// MI355X addition: one hypothesis of a beam run
+struct beam_hypothesis {
+    std::vector<int32_t> tokens;   // a trailing EOS popped
+    std::string text;
+    float sum_logprob = 0.f;       // the EOS step included
+    bool finished = false;         // ended in EOS (else the token budget ran out)
 };
 
 // src/qwen3_asr.h:37-49
@@ -53,6 +66,9 @@ struct transcribe_result {
     // token itself); empty otherwise
     std::vector<int32_t> alt_tokens;
     std::vector<float> alt_logprobs;
+    // MI355X addition (trailing): with transcribe_params::beam_width >= 2, every hypothesis of the clip,
+    // best first (tokens / text above are beams[0]'s); empty otherwise
+    std::vector<beam_hypothesis> beams;
 };
 
 using progress_callback_t = std::function<void(int tokens_generated, int max_tokens)>;
@@ -104,6 +120,7 @@ private:
     bool ensure_ctx(int batch, int n_ctx);
     bool set_logprobs(bool on);
     bool set_top_k(int k);
+    bool set_beam_width(int w);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

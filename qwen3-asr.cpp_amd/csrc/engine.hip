@@ -64,6 +64,7 @@ static const std::vector<FuseOption> &fuse_options() {
         {"token_logprobs", "QASR_TOKEN_LOGPROBS", &FuseCfg::token_logprobs},
         {"top_k", "QASR_TOP_K", &FuseCfg::top_k},
         {"lmh_topk", "QASR_LMH_TOPK", &FuseCfg::lmh_topk},
+        {"beam_width", "QASR_BEAM_WIDTH", &FuseCfg::beam_width},
     };
     return v;
 }
@@ -123,7 +124,7 @@ std::mutex &qasr::eng::device_lock(int device) {
 }
 
 // ---------------------------------------------------------------- buffers
-static int dev_alloc(qasr_ctx *c, void **p, size_t bytes) {
+int qasr::eng::dev_alloc(qasr_ctx *c, void **p, size_t bytes) {
     HIPCHK(hipMalloc(p, bytes ? bytes : 256));
     c->owned.push_back({*p, bytes});
     return 0;
@@ -149,7 +150,7 @@ int qasr::eng::ensure(qasr_ctx *c, DevBuf &b, size_t bytes) {
 
 // option top_k: its device buffers, sized for QASR_TOPK_MAX, the first time the option is non-zero
 static_assert(QASR_TOPK_MAX == qasr::TOPK_MAX, "the C-ABI's largest K is the row kernel's");
-static int ensure_topk(qasr_ctx *c) {
+int qasr::eng::ensure_topk(qasr_ctx *c) {
     if (c->d_tkpart) return 0;   // (the last of the five: set only once all are)
     const size_t step = (size_t)c->max_batch * QASR_TOPK_MAX * 4, hist = step * c->hist_cap;
     int32_t *id = nullptr, *hid = nullptr;
@@ -164,8 +165,28 @@ static int ensure_topk(qasr_ctx *c) {
     return 0;
 }
 
+static_assert(QASR_BEAM_MAX == qasr::TOPK_MAX, "a beam step ranks the row kernel's K = W alternatives");
+// option beam_width: the beam state (qasr_ctx::BeamDev) and the top-K buffers its steps read, the first time it is >= 2
+int qasr::eng::ensure_beam(qasr_ctx *c) {
+    if (c->bm.h_lp) return ensure_topk(c);   // (the last one allocated below)
+    const size_t rows = (size_t)c->max_batch * 4, hist = rows * c->hist_cap;
+    qasr_ctx::BeamDev b;
+    int rc;
+    if ((rc = ensure_topk(c)) || (rc = dev_alloc(c, (void **)&b.cum, rows)) || (rc = dev_alloc(c, (void **)&b.fin_sum, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.fin_lp, rows)) || (rc = dev_alloc(c, (void **)&b.fin_row, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.fin_t, rows)) || (rc = dev_alloc(c, (void **)&b.n_fin, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.done, rows)) || (rc = dev_alloc(c, (void **)&b.t, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.P, rows)) || (rc = dev_alloc(c, (void **)&b.eos, 4)) || (rc = dev_alloc(c, (void **)&b.parent, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.from, rows)) || (rc = dev_alloc(c, (void **)&b.to, rows)) ||
+        (rc = dev_alloc(c, (void **)&b.h_par, hist)) || (rc = dev_alloc(c, (void **)&b.h_id, hist)) ||
+        (rc = dev_alloc(c, (void **)&b.h_lp, hist)))
+        return rc;
+    c->bm = b;
+    return 0;
+}
+
 int qasr::eng::topk_step(qasr_ctx *c, int B) {
-    const int K = c->fuse.top_k;
+    const int K = step_k(c);
     if (K <= 0) return 0;
     if (!launch_topk_rows(c->d_logits, c->m->hp.vocab, B, 0, K, c->d_step, c->d_tkid, c->d_tklp, c->d_tkhid, c->d_tkhlp,
                           c->hist_cap, c->st))
@@ -299,7 +320,9 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
         (rc = dev_alloc(c.get(), (void **)&c->d_lphist, (size_t)B * max_ctx * 4)) ||
         (rc = dev_alloc(c.get(), (void **)&c->d_lppart, (size_t)lmhead_grid() * 128 * 8)))
         return rc;
+    if (c->fuse.beam_width < 0 || c->fuse.beam_width > QASR_BEAM_MAX) return fail(QASR_ERR_ARG, "QASR_BEAM_WIDTH out of range (0..8)");
     if (c->fuse.top_k && (rc = ensure_topk(c.get()))) return rc;
+    if (c->fuse.beam_width >= 2 && (rc = ensure_beam(c.get()))) return rc;
     std::vector<int> slots(B);
     for (int b = 0; b < B; b++) slots[b] = b;
     HIPCHK(hipMemcpy(c->d_slot, slots.data(), B * 4, hipMemcpyHostToDevice));
@@ -341,6 +364,11 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
         if (n == o.name) {
             if (n == "poll_limit" && value <= 0) return fail(QASR_ERR_ARG, "poll_limit must be positive");
             if (n == "top_k" && (value < 0 || value > QASR_TOPK_MAX)) return fail(QASR_ERR_ARG, "top_k out of range (0..8)");
+            if (n == "beam_width" && (value < 0 || value > QASR_BEAM_MAX)) return fail(QASR_ERR_ARG, "beam_width out of range (0..8)");
+            if (n == "beam_width" && value >= 2) {
+                HIPCHK(hipSetDevice(c->m->device));
+                if (const int rc = ensure_beam(c)) return rc;
+            }
             if (n == "top_k" && value > 0) {
                 HIPCHK(hipSetDevice(c->m->device));
                 if (const int rc = ensure_topk(c)) return rc;
@@ -351,6 +379,10 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
                 c->lp_step_B = c->lp_run_B = c->lp_run_T = 0;
                 c->lp_run.clear();
                 c->lp_run_n.clear();
+            }
+            if (o.field == &FuseCfg::beam_width) {
+                c->last_run_beam = false;
+                c->beam_res.clear();
             }
             if (o.field == &FuseCfg::top_k) {
                 c->tk_step_B = c->tk_run_B = c->tk_run_T = 0;

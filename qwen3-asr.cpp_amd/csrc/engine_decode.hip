@@ -58,8 +58,10 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     if (lp && !lmh_one) want_logits = true;
     // option top_k: inside the one-launch LM head at 9 .. 64 rows where that measured faster (lmhead.hip TK; FuseCfg::lmh_topk);
     // every other path writes its logits, then the row kernel after the bookkeeping (the one-launch heads write them too)
-    const bool tk = c->fuse.top_k > 0;
-    const bool tk_fused = tk && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && c->fuse.top_k <= kLmhTopkAutoMax));
+    // (a beam run: K = its width, whatever option top_k says)
+    const int K = step_k(c);
+    const bool tk = K > 0;
+    const bool tk_fused = tk && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && K <= kLmhTopkAutoMax));
     if (tk && !tk_fused) want_logits = true;
     int rc;
     const size_t layer_kv = (size_t)c->max_batch * hp.n_kv_head * c->max_ctx * 128;
@@ -237,7 +239,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
                 if (lp || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
                 if (tk_fused) {
                     lm.tk_part = c->d_tkpart; lm.tk_out = c->d_tkid; lm.tk_lp = c->d_tklp; lm.tk_hist = c->d_tkhid;
-                    lm.tk_lphist = c->d_tkhlp; lm.tk_k = c->fuse.top_k;
+                    lm.tk_lphist = c->d_tkhlp; lm.tk_k = K;
                 }
                 if (!launch_lmhead_batch(lm, s))   // (lmh_one mirrors its shape conditions: never expected)
                     return fail(QASR_ERR_STATE, "decode step: the batched LM head declined B = " + std::to_string(B));
@@ -259,6 +261,10 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         if (tk && (rc = topk_step(c, B))) return rc;
         launch_fill_u64(c->d_amax, B, 0ull, s);   // re-arm (zero at rest)
     }
+    // a beam run: the beam step replaces the greedy choice in d_tok, then the fork (the grid covers the bucket's keys)
+    if (c->beam_W >= 2 && r.in(skinny || lmh_one ? 1 + 2 * nl : 2 + 2 * nl) &&
+        (rc = beam_step(c, B / c->beam_W, (std::min(c->max_ctx, splits * decode_split_len()) + 7) / 8)))
+        return rc;
     return declined_check("decode step");
 }
 
@@ -339,7 +345,7 @@ int qasr::eng::decode_graph(qasr_ctx *c, int B, bool want_logits, int base) {
 
 static int step_graphs(qasr_ctx *c, int splits, qasr_ctx::StepGraphs **out) {
     const int B = c->graph_B;
-    auto &gs = c->graphs[B * 65536 + splits];
+    auto &gs = c->graphs[std::make_tuple(c->beam_W, B, splits)];   // (a beam run's steps are graphs of their own)
     int rc;
     if (!gs.full && (rc = capture(c, B, c->graph_logits, kWholeStep, splits, &gs.full))) return rc;
     if (c->probe && !gs.pre) {

@@ -6,6 +6,7 @@
 //   engine_stages.hip  mel, encoder, prefill (run_* and their qasr_* entry points), Q8_0 GEMM helpers
 //   engine_decode.hip  the decode-step emitter, graph capture, kernel probes, qasr_decode_step
 //   engine_run.hip     qasr_run, the continuous-batching stream, their log-probability readers
+//   engine_beam.hip    beam search: the KV-cache fork entry, the beam loop, the hypothesis reader
 //   engine_align.hip   the forced aligner and its JSON output
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,11 +19,13 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/qasr_capi.h"
 #include "../host/gguf.h"
 #include "../host/qasr_host.h"
+#include "beam_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -170,6 +173,22 @@ struct qasr_ctx {
     int tk_run_B = 0, tk_run_T = 0;
     const std::vector<int32_t> *tk_sink_id = nullptr;   // inside a qasr_sink_fn call: the delivered clip's alternatives
     const std::vector<float> *tk_sink_lp = nullptr;
+    // option beam_width (W = fuse.beam_width >= 2): beam search in qasr_run (engine_beam.hip).  Clip g owns rows
+    // g * W .. g * W + W - 1.  The device state is allocated the first time the option is >= 2 (ensure_beam):
+    // per row the summed log-probability, the fork arguments and the group's finished table at g * W; per group
+    // n_fin / done / t / P; the back-pointer history [hist_cap][max_batch] of (parent row, token, logprob)
+    struct BeamDev {
+        float *cum = nullptr, *fin_sum = nullptr, *fin_lp = nullptr, *h_lp = nullptr;
+        int *fin_row = nullptr, *fin_t = nullptr, *n_fin = nullptr, *done = nullptr, *t = nullptr, *P = nullptr;
+        int32_t *eos = nullptr;        // [1] the run's EOS id, -1 with ignore_eos (read by the captured beam step)
+        int *parent = nullptr, *from = nullptr, *to = nullptr, *h_par = nullptr;
+        int32_t *h_id = nullptr;
+    } bm;
+    int beam_W = 0;                    // inside a beam run: its width (the decode step then ends with the beam step and
+                                       // the fork, and its top-K runs with K = W); else 0
+    bool last_run_beam = false;        // the last qasr_run was a beam run (qasr_get_logprobs / qasr_get_topk refuse)
+    std::vector<std::vector<qasr::BeamHyp>> beam_res;   // its hypotheses per clip, best first
+    DevBuf fork_args;                  // qasr_kv_fork: the caller's parent | from | to on the device
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -219,7 +238,7 @@ struct qasr_ctx {
     // decode graphs, one set per attention split-grid bucket (the grid must
     // cover the longest sequence's context: it grows by 64 keys per split)
     struct StepGraphs { hipGraphExec_t full = nullptr, pre = nullptr, post = nullptr; };
-    std::map<int, StepGraphs> graphs;   // key: batch * 65536 + split bucket
+    std::map<std::tuple<int, int, int>, StepGraphs> graphs;   // key: (beam_W, batch, split bucket)
     int graph_B = -1;
     bool graph_logits = false;
     int graph_base = 0;            // max prompt length of the current run: step k feeds position base + k
@@ -260,6 +279,11 @@ int stage_pinned(qasr_ctx *c, const void *src, size_t bytes, void *dst);
 // option top_k after the greedy bookkeeping of a prefill or decode step (d_step names the slot of the
 // token just written to d_hist): the step's alternatives from the fp32 logits in d_logits
 int topk_step(qasr_ctx *c, int B);
+// K of the step's top-K: the beam width inside a beam run, else option top_k
+inline int step_k(const qasr_ctx *c) { return c->beam_W >= 2 ? c->beam_W : c->fuse.top_k; }
+int ensure_topk(qasr_ctx *c);
+int ensure_beam(qasr_ctx *c);
+int dev_alloc(qasr_ctx *c, void **p, size_t bytes);
 
 // V^T cache elements of one layer
 inline size_t layer_vt(const qasr_ctx *c) {
@@ -297,6 +321,26 @@ int prefill_layers(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vect
 int run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vector<int> &P, const float *d_feats,
                 const std::vector<int> &audio_pos, const std::vector<int> &N, bool want_logits,
                 const std::vector<int> *slots = nullptr, const std::vector<int> *pos0 = nullptr);
+
+// a roctx range for the lifetime of the object (rocprofv3 --marker-trace); engine_run.hip
+struct RoctxRange {
+    explicit RoctxRange(const char *name);
+    ~RoctxRange();
+    RoctxRange(const RoctxRange &) = delete;
+    RoctxRange &operator=(const RoctxRange &) = delete;
+};
+
+// engine_run.hip
+struct FrontEnd {
+    std::vector<int> P, audio_pos, Nb;   // per clip: prompt length, first audio row, encoder frames
+};
+int front_end_staged(qasr_ctx *c, int max_tokens, const std::vector<int> *slots, FrontEnd &fe);
+int run_timings(qasr_ctx *c, int steps, qasr_timings *t);
+
+// engine_beam.hip
+int beam_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
+// the beam step and the fork that end a decode step of a beam run (blocks: 8-key blocks the fork's grid covers)
+int beam_step(qasr_ctx *c, int G, int blocks);
 
 // engine_decode.hip
 int split_bucket(qasr_ctx *c, int pos);

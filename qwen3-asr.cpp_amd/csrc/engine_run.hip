@@ -11,15 +11,8 @@
 using namespace qasr;
 using namespace qasr::eng;
 
-namespace {
-// a roctx range for the lifetime of the object (rocprofv3 --marker-trace)
-struct RoctxRange {
-    explicit RoctxRange(const char *name) { roctxRangePushA(name); }
-    ~RoctxRange() { roctxRangePop(); }
-    RoctxRange(const RoctxRange &) = delete;
-    RoctxRange &operator=(const RoctxRange &) = delete;
-};
-}  // namespace
+qasr::eng::RoctxRange::RoctxRange(const char *name) { roctxRangePushA(name); }
+qasr::eng::RoctxRange::~RoctxRange() { roctxRangePop(); }
 
 extern "C" int qasr_stage_audio(qasr_ctx *c, const float *const *pcm, const int *n, int B) {
     if (!c || !pcm || !n || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
@@ -41,11 +34,6 @@ extern "C" int qasr_stage_audio(qasr_ctx *c, const float *const *pcm, const int 
 // it, after the encoder and (e_prefill, optional) after the prefill.
 // check_prompt(r, P, audio_pos) sees every prompt before the prefill is
 // launched; a non-zero return ends the call with it.
-namespace {
-struct FrontEnd {
-    std::vector<int> P, audio_pos, Nb;   // per clip: prompt length, first audio row, encoder frames
-};
-}  // namespace
 static int front_end(qasr_ctx *c, const float *d_pcm, const std::vector<long> &off, const std::vector<int> &n, hipEvent_t e_start,
                      hipEvent_t e_mel, hipEvent_t e_enc, hipEvent_t e_prefill, const std::vector<int> *slots,
                      const std::function<int(int, int, int)> &check_prompt, FrontEnd &o) {
@@ -152,6 +140,20 @@ static int greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::
     return 0;
 }
 
+// the stage timings of a run from its events (t may be null)
+int qasr::eng::run_timings(qasr_ctx *c, int steps, qasr_timings *t) {
+    if (!t) return 0;
+    float a, b2, c2, d;
+    (void)hipEventElapsedTime(&a, c->ev[EV_START], c->ev[EV_MEL]);
+    (void)hipEventElapsedTime(&b2, c->ev[EV_MEL], c->ev[EV_ENC]);
+    (void)hipEventElapsedTime(&c2, c->ev[EV_ENC], c->ev[EV_PREFILL]);
+    (void)hipEventElapsedTime(&d, c->ev[EV_PREFILL], c->ev[EV_END]);
+    t->t_mel_ms = a; t->t_encode_ms = b2; t->t_prefill_ms = c2; t->t_decode_ms = d;
+    t->t_total_ms = (double)a + b2 + c2 + d;
+    t->n_decode_steps = steps;
+    return 0;
+}
+
 // after the timed span of a run: the device error word, probe and profile
 // records, then the history's rows as the caller's tokens (and their
 // log-probabilities, option token_logprobs) and the stage timings
@@ -238,23 +240,27 @@ static int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const
     }
     if (lp) { c->lp_run_B = B; c->lp_run_T = max_tokens; }
     if (K) { c->tk_run_B = B; c->tk_run_T = max_tokens; }
-    if (t) {
-        float a, b2, c2, d;
-        (void)hipEventElapsedTime(&a, c->ev[EV_START], c->ev[EV_MEL]);
-        (void)hipEventElapsedTime(&b2, c->ev[EV_MEL], c->ev[EV_ENC]);
-        (void)hipEventElapsedTime(&c2, c->ev[EV_ENC], c->ev[EV_PREFILL]);
-        (void)hipEventElapsedTime(&d, c->ev[EV_PREFILL], c->ev[EV_END]);
-        t->t_mel_ms = a; t->t_encode_ms = b2; t->t_prefill_ms = c2; t->t_decode_ms = d;
-        t->t_total_ms = (double)a + b2 + c2 + d;
-        t->n_decode_steps = steps;
-    }
+    if ((rc = run_timings(c, steps, t))) return rc;
     return 0;
+}
+
+// the front end over the staged clips of a run (slots: prefill_layers' slot map), with the reference's two prompt checks
+int qasr::eng::front_end_staged(qasr_ctx *c, int max_tokens, const std::vector<int> *slots, FrontEnd &fe) {
+    auto check_prompt = [&](int, int P, int audio_pos) -> int {   // the reference's two messages
+        if (audio_pos < 0) return fail(QASR_ERR_ARG, "No audio_pad token found in input sequence");
+        if (P + max_tokens > c->max_ctx) return fail(QASR_ERR_ARG, "Context length exceeded (prompt + max_tokens > max_ctx)");
+        return 0;
+    };
+    return front_end(c, c->pcm.as<float>(), c->staged_off, c->staged_n, c->ev[EV_START], c->ev[EV_MEL], c->ev[EV_ENC],
+                     c->ev[EV_PREFILL], slots, check_prompt, fe);
 }
 
 extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t) {
     if (!c || max_tokens <= 0 || !tokens || !n_tokens) return fail(QASR_ERR_ARG, "bad arguments");
     const int B = (int)c->staged_n.size();
     if (B == 0) return fail(QASR_ERR_STATE, "no staged audio");
+    if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return beam_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
+    c->last_run_beam = false;
     if (B > c->max_batch) return fail(QASR_ERR_ARG, "staged clips exceed the context's max_batch (qasr_run_staged runs subsets)");
     HIPCHK(hipSetDevice(c->m->device));
     std::unique_lock<std::mutex> dev_lk;
@@ -270,14 +276,7 @@ extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *to
     RoctxRange run_range("qasr.run");   // host-side ranges for rocprofv3 --marker-trace
     int rc;
     FrontEnd fe;
-    auto check_prompt = [&](int, int P, int audio_pos) -> int {   // the reference's two messages
-        if (audio_pos < 0) return fail(QASR_ERR_ARG, "No audio_pad token found in input sequence");
-        if (P + max_tokens > c->max_ctx) return fail(QASR_ERR_ARG, "Context length exceeded (prompt + max_tokens > max_ctx)");
-        return 0;
-    };
-    if ((rc = front_end(c, c->pcm.as<float>(), c->staged_off, c->staged_n, c->ev[EV_START], c->ev[EV_MEL], c->ev[EV_ENC],
-                        c->ev[EV_PREFILL], nullptr, check_prompt, fe)))
-        return rc;
+    if ((rc = front_end_staged(c, max_tokens, nullptr, fe))) return rc;
     c->run_P = fe.P;
     if ((rc = decode_graph(c, B, false, *std::max_element(fe.P.begin(), fe.P.end())))) return rc;
     if ((rc = probe_arm(c, max_tokens - 1))) return rc;
@@ -339,6 +338,7 @@ struct StreamClip {
 static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamClip &)> &next, qasr_sink_fn sink, void *user,
                       int max_tokens, int ignore_eos, qasr_stream_stats *stats) {
     if (!c || !sink || max_tokens <= 0 || slots < 0 || slots > c->max_batch) return fail(QASR_ERR_ARG, "bad arguments");
+    if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return fail(QASR_ERR_STATE, "the continuous-batching stream has no beam search (option beam_width >= 2)");
     HIPCHK(hipSetDevice(c->m->device));
     const int S = slots ? slots : c->max_batch;
     std::unique_lock<std::mutex> dev_lk;
@@ -587,6 +587,7 @@ extern "C" int qasr_run_stream_staged(qasr_ctx *c, int slots, qasr_fetch_staged_
 extern "C" int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens) {
     if (!c || !out || B <= 0 || max_tokens <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     if (!c->fuse.token_logprobs) return fail(QASR_ERR_STATE, "option token_logprobs is off");
+    if (c->last_run_beam) return fail(QASR_ERR_STATE, "the last run was a beam run: its values are qasr_get_beams'");
     if (!c->lp_run_B) return fail(QASR_ERR_STATE, "no run has finished with option token_logprobs on");
     if (B < c->lp_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
     for (int b = 0; b < c->lp_run_B; b++)
@@ -611,6 +612,7 @@ extern "C" int qasr_get_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, 
     if (!c || !ids || !logprobs || B <= 0 || max_tokens <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     if (!c->fuse.top_k) return fail(QASR_ERR_STATE, "option top_k is off");
     if (K != c->fuse.top_k) return fail(QASR_ERR_ARG, "K differs from option top_k");
+    if (c->last_run_beam) return fail(QASR_ERR_STATE, "the last run was a beam run: its values are qasr_get_beams'");
     if (!c->tk_run_B) return fail(QASR_ERR_STATE, "no run has finished with option top_k on");
     if (B < c->tk_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
     for (int b = 0; b < c->tk_run_B; b++)

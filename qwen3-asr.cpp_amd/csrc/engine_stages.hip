@@ -403,7 +403,7 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     launch_rmsnorm_f16(x, H, c->plast.as<int>(), B, H, m->out_norm, hp.rms_eps, xl, s);
     launch_fill_u64(c->d_amax, B, 0ull, s);
     const bool lp = c->fuse.token_logprobs != 0;   // the log-probabilities come from the fp32 logits
-    want_logits = want_logits || lp || c->fuse.top_k > 0;   // (option top_k: its alternatives likewise)
+    want_logits = want_logits || lp || step_k(c) > 0;   // (option top_k or a beam run: the alternatives likewise)
     if (B <= 8) {
         GemvArgs gv{};
         gv.xh = xl; gv.ldxh = H; gv.W = m->embd; gv.K = H; gv.N = hp.vocab; gv.M = B;
@@ -602,8 +602,10 @@ extern "C" int qasr_encoder_frames_no_chunk(int n_mel_frames) {
 // when they fit inside it, as the reference's condition.
 // n_past == nullptr is qasr_prefill: every sequence from position 0, with the
 // plain prefill's attention arguments (no seq_pos0) and its laxer argument rules.
+// slots (qasr_prefill_slots): sequence b's KV-cache slot; nullptr = slot b
 static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, const float *feats,
-                                const int *audio_pos, const int *N, int B, float *logits_last, int32_t *argmax) {
+                                const int *audio_pos, const int *N, int B, float *logits_last, int32_t *argmax,
+                                const int *slots = nullptr) {
     if (!c || !ids || !P || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     if (n_past) {
         if (feats && (!N || !audio_pos)) return fail(QASR_ERR_ARG, "audio features need N and audio_pos");
@@ -625,12 +627,14 @@ static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, c
     for (long i = 0; i < nid; i++)
         if (ids[i] < 0 || ids[i] >= c->m->hp.vocab) return fail(QASR_ERR_ARG, "token id out of range");
     std::vector<int32_t> idv(ids, ids + nid);
+    std::vector<int> sl;
+    if (slots) sl.assign(slots, slots + B);   // (prefill_layers checks their range)
     int rc;
     if (nf) {
         if ((rc = ensure(c, c->feats, (size_t)nf * H * 4))) return rc;
         HIPCHK(hipMemcpyAsync(c->feats.p, feats, (size_t)nf * H * 4, hipMemcpyHostToDevice, c->st));
     }
-    if ((rc = run_prefill(c, idv, Pv, nf ? c->feats.as<float>() : nullptr, ap, Nv, logits_last != nullptr, nullptr,
+    if ((rc = run_prefill(c, idv, Pv, nf ? c->feats.as<float>() : nullptr, ap, Nv, logits_last != nullptr, slots ? &sl : nullptr,
                           n_past ? &p0 : nullptr)))
         return rc;
     if (logits_last) HIPCHK(hipMemcpyAsync(logits_last, c->d_logits, (size_t)B * c->m->hp.vocab * 4, hipMemcpyDeviceToHost, c->st));
@@ -644,6 +648,12 @@ static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, c
 extern "C" int qasr_prefill(qasr_ctx *c, const int32_t *ids, const int *P, const float *feats, const int *audio_pos,
                             const int *N, int B, float *logits_last, int32_t *argmax) {
     return prefill_chunk_common(c, ids, P, nullptr, feats, audio_pos, N, B, logits_last, argmax);
+}
+
+extern "C" int qasr_prefill_slots(qasr_ctx *c, const int32_t *ids, const int *P, const float *feats, const int *audio_pos,
+                                  const int *N, const int *slots, int B, float *logits_last, int32_t *argmax) {
+    if (!slots) return fail(QASR_ERR_ARG, "bad arguments");
+    return prefill_chunk_common(c, ids, P, nullptr, feats, audio_pos, N, B, logits_last, argmax, slots);
 }
 
 extern "C" int qasr_prefill_chunk(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, int B, float *logits_last,

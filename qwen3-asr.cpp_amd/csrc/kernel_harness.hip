@@ -225,3 +225,102 @@ extern "C" int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a) {
     if ((rc = get(q, a->q)) || (rc = get(d, a->d))) return rc;
     return 0;
 }
+
+// ------------------------------------------------------------- beam search
+namespace {
+// an in / out array between two 4 KiB fences of 0xFF bytes the launch must leave alone
+struct KtFenced {
+    static constexpr size_t kFence = 4096;
+    KtBuf b;
+    size_t bytes = 0;
+    int put(const void *host, size_t n) {
+        bytes = n;
+        b.bytes = n + 2 * kFence;
+        b.off = kFence;
+        HIPCHK(hipMalloc((void **)&b.d, b.bytes));
+        HIPCHK(hipMemset(b.d, 0xFF, b.bytes));
+        HIPCHK(hipMemcpy(b.d + kFence, host, n, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int take(void *host, const char *name) {
+        std::vector<unsigned char> all(b.bytes);
+        HIPCHK(hipMemcpy(all.data(), b.d, b.bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < kFence; i++)
+            if (all[i] != 0xFF || all[kFence + bytes + i] != 0xFF) return fail(QASR_ERR_STATE, std::string("a write outside ") + name);
+        memcpy(host, all.data() + kFence, bytes);
+        return 0;
+    }
+};
+
+int finish_plain(int32_t *declined, bool ran) {
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipDeviceSynchronize();
+    if (le != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (se != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel run: ") + hipGetErrorString(se));
+    *declined = ran ? 0 : 1;
+    return 0;
+}
+}  // namespace
+
+extern "C" int qasr_kt_kv_fork(int device, qasr_kt_kv_fork_args *a) {
+    if (!a || !a->kc || !a->vc || !a->vt || !a->parent || !a->from || !a->to || a->layers <= 0 || a->n_kv_head <= 0 || a->max_ctx <= 0 ||
+        a->slots <= 0 || a->guard < 0 || a->B <= 0 || a->B > a->slots || a->blocks < 0)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    // (the kernel clamps ranges to [0, max_ctx] and follows no parent outside a row's group; B <= slots keeps every row inside)
+    int rc = use_device(device);
+    if (rc) return rc;
+    const size_t S = (size_t)a->slots + a->guard;
+    const size_t kv = (size_t)a->layers * S * a->n_kv_head * a->max_ctx * 128 * 2, vt = (size_t)a->layers * S * a->n_kv_head * 128 * vt_ctx(a->max_ctx) * 2;
+    KtFenced kc, vc, vtb;
+    KtBuf par, frm, to;
+    if ((rc = kc.put(a->kc, kv)) || (rc = vc.put(a->vc, kv)) || (rc = vtb.put(a->vt, vt)) || (rc = put_state(par, a->parent, (size_t)a->B * 4)) ||
+        (rc = put_state(frm, a->from, (size_t)a->B * 4)) || (rc = put_state(to, a->to, (size_t)a->B * 4)))
+        return rc;
+    KvForkArgs f{};
+    f.kc = kc.b.ptr<uint16_t>(); f.vc = vc.b.ptr<uint16_t>(); f.vt = vtb.b.ptr<uint16_t>();
+    f.layers = a->layers; f.n_kv_head = a->n_kv_head; f.max_ctx = a->max_ctx; f.slots = (int)S;
+    f.parent = par.ptr<int>(); f.from = frm.ptr<int>(); f.to = to.ptr<int>();
+    f.B = a->B; f.group = a->group; f.blocks = a->blocks ? a->blocks : (a->max_ctx + 7) / 8;
+    const bool ran = launch_kv_fork(f, nullptr);
+    if ((rc = finish_plain(&a->declined, ran))) return rc;
+    if ((rc = kc.take(a->kc, "kc")) || (rc = vc.take(a->vc, "vc")) || (rc = vtb.take(a->vt, "vt"))) return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_beam_select(int device, qasr_kt_beam_select_args *a) {
+    if (!a || a->W < 2 || a->W > QASR_BEAM_MAX || a->G <= 0 || a->t < 0 || a->guard < 0 || !a->ids || !a->lps || !a->P || !a->cum ||
+        !a->fin_row || !a->fin_t || !a->fin_sum || !a->fin_lp || !a->n_fin || !a->done || !a->t_out || !a->tok || !a->parent ||
+        !a->from || !a->to || !a->h_par || !a->h_id || !a->h_lp)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int R = a->G * a->W, G = a->G;
+    std::vector<int> tv(G, a->t);
+    KtBuf ids, lps, P, cum, fr, ft, fs, fl, nf, dn, t, tok, par, frm, to, hp, hi, hl, eos;
+    if ((rc = put_in(ids, a->ids, R, a->W, 4, a->guard, 0xFF)) || (rc = put_in(lps, a->lps, R, a->W, 4, a->guard, 0xFF)) ||
+        (rc = put_state(P, a->P, (size_t)G * 4)) || (rc = put_state(cum, a->cum, (size_t)R * 4)) ||
+        (rc = put_state(fr, a->fin_row, (size_t)R * 4)) || (rc = put_state(ft, a->fin_t, (size_t)R * 4)) ||
+        (rc = put_state(fs, a->fin_sum, (size_t)R * 4)) || (rc = put_state(fl, a->fin_lp, (size_t)R * 4)) ||
+        (rc = put_state(nf, a->n_fin, (size_t)G * 4)) || (rc = put_state(dn, a->done, (size_t)G * 4)) ||
+        (rc = put_state(t, tv.data(), (size_t)G * 4)) || (rc = put_state(eos, &a->eos, 4)) || (rc = put_out(tok, a->tok, 1, R, 4, a->guard)) ||
+        (rc = put_out(par, a->parent, 1, R, 4, a->guard)) || (rc = put_out(frm, a->from, 1, R, 4, a->guard)) ||
+        (rc = put_out(to, a->to, 1, R, 4, a->guard)) || (rc = put_out(hp, a->h_par, 1, R, 4, a->guard)) ||
+        (rc = put_out(hi, a->h_id, 1, R, 4, a->guard)) || (rc = put_out(hl, a->h_lp, 1, R, 4, a->guard)))
+        return rc;
+    BeamSelectArgs s{};
+    s.tk_id = ids.ptr<int32_t>(); s.tk_lp = lps.ptr<float>();
+    s.cum = cum.ptr<float>(); s.fin_row = fr.ptr<int>(); s.fin_t = ft.ptr<int>(); s.fin_sum = fs.ptr<float>(); s.fin_lp = fl.ptr<float>();
+    s.n_fin = nf.ptr<int>(); s.done = dn.ptr<int>(); s.t = t.ptr<int>(); s.P = P.ptr<int>();
+    s.tok = tok.ptr<int32_t>(); s.parent = par.ptr<int>(); s.from = frm.ptr<int>(); s.to = to.ptr<int>();
+    s.h_par = hp.ptr<int>(); s.h_id = hi.ptr<int32_t>(); s.h_lp = hl.ptr<float>();
+    s.hist_stride = R; s.hist_base = a->t;   // the one history slot the buffers hold
+    s.W = a->W; s.G = G; s.eos = eos.ptr<int32_t>();
+    const bool ran = launch_beam_select(s, nullptr);
+    if ((rc = finish_plain(&a->declined, ran))) return rc;
+    if ((rc = get(cum, a->cum)) || (rc = get(fr, a->fin_row)) || (rc = get(ft, a->fin_t)) || (rc = get(fs, a->fin_sum)) ||
+        (rc = get(fl, a->fin_lp)) || (rc = get(nf, a->n_fin)) || (rc = get(dn, a->done)) || (rc = get(t, a->t_out)) ||
+        (rc = get(tok, a->tok)) || (rc = get(par, a->parent)) || (rc = get(frm, a->from)) || (rc = get(to, a->to)) ||
+        (rc = get(hp, a->h_par)) || (rc = get(hi, a->h_id)) || (rc = get(hl, a->h_lp)))
+        return rc;
+    return 0;
+}

@@ -240,6 +240,8 @@ struct FuseCfg {
                                         // (id, log-probability) pairs (qasr_get_*topk): from the fp32 logits by
                                         // launch_topk_rows (the step then writes its logits), or inside the one-launch
                                         // LM head (lmh_topk above); 0: nothing changes
+    int beam_width = 0;                 // W in 2 .. 8: qasr_run decodes by beam search of width W (engine_beam.hip);
+                                        // 0 / 1: greedy, nothing changes
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
@@ -432,5 +434,40 @@ bool launch_topk_rows(const float *logits, int ld, int B, int n_valid, int K, co
 void launch_gather_rows(const float *src, const int *idx, int rows, int D, float *dst, hipStream_t s);
 // decode-step bookkeeping on device: n_kv[b] += 1, row_pos[b] += 1, step += 1
 void launch_step_advance(int *row_pos, int *n_kv, int *step, int B, hipStream_t s);
+
+// ---------------------------------------------------------------- beam search (beam.hip)
+// KV-cache fork: rows are forked inside groups of `group` consecutive rows (1 .. 8, B a multiple of
+// it, parent[b] in b's group).  After the launch positions [from[b], to[b]) of cache slot b -- K, V
+// and V^T, every layer and kv head -- hold what slot parent[b] held there before it; everything else
+// (other positions, also inside a partly covered 8-key V^T block, the V^T slack, slots >= B) is
+// unchanged.  parent / from / to are device arrays read by the kernel; the grid covers `blocks`
+// 8-key blocks, so blocks * 8 must reach the largest to[b] the launch can meet.
+struct KvForkArgs {
+    uint16_t *kc, *vc, *vt;              // cache bases: [layers][slots][n_kv_head][max_ctx][128], V^T likewise (vt_ctx)
+    int layers, n_kv_head, max_ctx, slots;
+    const int *parent, *from, *to;       // [B]
+    int B, group, blocks;
+};
+bool launch_kv_fork(const KvForkArgs &a, hipStream_t s);   // false = bad shape, nothing launched
+// Beam step: G groups of W rows (row g * W + i).  Reads the step's W best (id, logprob) pairs of every
+// row (tk_id / tk_lp [rows][W]; at a group's first step, t = 0, row g of them: the prefill's one row a
+// clip) and the group state, writes the next live rows' tokens, the fork arguments and one slot of the
+// back-pointer history (slot t - hist_base).  W in 2 .. 8.  *eos (device memory, so that a captured step
+// serves runs with either setting) < 0: no token ends a hypothesis.
+struct BeamSelectArgs {
+    const int32_t *tk_id; const float *tk_lp;
+    float *cum;                          // [rows] summed log-probability of each live row
+    int *fin_row, *fin_t; float *fin_sum, *fin_lp;   // [rows]: group g's finished table at g * W: the row that emitted
+                                         // EOS, the step, the sum with it, the EOS step's log-probability
+    int *n_fin, *done, *t;               // [G]: finished entries, 0 or the step count at which the table filled, step index
+    const int *P;                        // [G] prompt lengths
+    int32_t *tok;                        // [rows] the tokens the next decode step feeds
+    int *parent, *from, *to;             // [rows] -> KvForkArgs
+    int *h_par; int32_t *h_id; float *h_lp;   // [slots][hist_stride]: (parent row, token, logprob) of each new live row
+    int hist_stride, hist_base;
+    int W, G;
+    const int32_t *eos;                  // [1]
+};
+bool launch_beam_select(const BeamSelectArgs &a, hipStream_t s);
 
 }  // namespace qasr

@@ -34,6 +34,8 @@ struct cli_params {
     bool print_progress = false, print_timing = true, print_tokens = false, profile = false;
     bool logprobs = false;   // --logprobs: per-token log-probabilities (transcribe_params::token_logprobs)
     int32_t top_k = 0;       // --top-k: alternatives per token (transcribe_params::top_k)
+    int32_t beam_width = 0;  // --beam-width: beam search of this width (transcribe_params::beam_width)
+    bool beams = false;      // --beams: list every hypothesis of a beam run
     bool align_mode = false, transcribe_align_mode = false;
 };
 
@@ -50,6 +52,8 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --tokens               Print token IDs\n");
     fprintf(stderr, "  --logprobs             Per-token log-probabilities: avg / min per file, and with --tokens each token's\n");
     fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
+    fprintf(stderr, "  --beam-width <n>       Beam search of width n (2..8) instead of greedy decoding\n");
+    fprintf(stderr, "  --beams                With --beam-width: list every hypothesis with its summed log-probability\n");
     fprintf(stderr, "  --profile              Print timing profile\n");
     fprintf(stderr, "  --device <n>           HIP device index (default: 0)\n");
     fprintf(stderr, "  --file-list <path>     Text file with one audio path per line (added to the -f files)\n");
@@ -110,6 +114,12 @@ static bool parse(int argc, char **argv, cli_params &p) {
             p.top_k = atoi(v.c_str());
             if (p.top_k < 1 || p.top_k > 8) { fprintf(stderr, "Error: --top-k takes 1..8\n"); return false; }
         }
+        else if (!strcmp(a, "--beam-width")) {
+            if (!val(v)) return false;
+            p.beam_width = atoi(v.c_str());
+            if (p.beam_width < 2 || p.beam_width > 8) { fprintf(stderr, "Error: --beam-width takes 2..8\n"); return false; }
+        }
+        else if (!strcmp(a, "--beams")) p.beams = true;
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
         else if (!strcmp(a, "-a") || !strcmp(a, "--transcribe-align")) p.transcribe_align_mode = true;
@@ -411,6 +421,7 @@ static int run_transcription(const cli_params &p) {
     tp.print_timing = p.print_timing;
     tp.token_logprobs = p.logprobs;
     tp.top_k = p.top_k;
+    tp.beam_width = p.beam_width;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));
@@ -442,6 +453,14 @@ static int run_transcription(const cli_params &p) {
                     }
             }
             fprintf(stderr, "\n");
+        }
+        if (p.beams && !r.beams.empty()) {
+            fprintf(stderr, "%s: %zu hypotheses\n", p.audio_paths[f].c_str(), r.beams.size());
+            for (size_t i = 0; i < r.beams.size(); ++i) {
+                const auto &h = r.beams[i];
+                fprintf(stderr, "  [%zu] %.4f  %zu tokens%s  \"%s\"\n", i, h.sum_logprob, h.tokens.size(), h.finished ? "" : " (unfinished)",
+                        h.text.c_str());
+            }
         }
         if (lp && !r.tokens.empty()) {
             double sum = 0.0;

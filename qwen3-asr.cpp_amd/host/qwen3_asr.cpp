@@ -122,6 +122,17 @@ bool Qwen3ASR::set_top_k(int k) {
     return true;
 }
 
+// context option beam_width likewise (0 and 1 both mean greedy)
+bool Qwen3ASR::set_beam_width(int w) {
+    int cur = 0;
+    if (qasr_ctx_get_option(ctx_, "beam_width", &cur) == 0 && cur == w) return true;
+    if (qasr_ctx_set_option(ctx_, "beam_width", w) != 0) {
+        error_msg_ = std::string("Failed to set beam_width: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
 transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const transcribe_params &params) {
     transcribe_result result;
     if (!model_) { result.error_msg = "Model not loaded"; return result; }
@@ -166,8 +177,11 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         sys.resize(std::max(k, 0));
         qasr_tokenize(model_, params.system_prompt.c_str(), sys.data(), k);
     }
-    if (!ensure_ctx(B, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
-        !set_top_k(params.top_k)) {
+    // beam search: W decode rows a clip, no per-token progress, its values through qasr_get_beams
+    const int W = params.beam_width >= 2 ? params.beam_width : 1;
+    const bool beam = W >= 2;
+    if (!ensure_ctx(B * W, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
+        !set_top_k(params.top_k) || !set_beam_width(params.beam_width)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -177,7 +191,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     std::vector<int> nt(B);
     qasr_timings tm{};
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
-    const bool per_token = progress_callback_ || params.print_progress;
+    const bool per_token = !beam && (progress_callback_ || params.print_progress);
     qasr_set_token_callback(ctx_, per_token ? token_cb : nullptr, per_token ? &tcb : nullptr);
     const int rc = qasr_transcribe_batch(ctx_, ptr.data(), n.data(), B, params.max_tokens, 0, toks.data(), nt.data(), &tm);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
@@ -192,15 +206,16 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         rep.resize(std::max(len, 0));
         profile_report_ = rep;
     }
+    const bool want_lp = params.token_logprobs && !beam;
     std::vector<float> lps;
-    if (params.token_logprobs) {
+    if (want_lp) {
         lps.resize((size_t)B * params.max_tokens);
         if (qasr_get_logprobs(ctx_, lps.data(), B, params.max_tokens) != 0) {
             for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
             return out;
         }
     }
-    const int K = params.top_k;
+    const int K = beam ? 0 : params.top_k;
     std::vector<int32_t> alt_id;
     std::vector<float> alt_lp;
     if (K > 0) {
@@ -215,18 +230,39 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     for (int b = 0; b < B; b++) {
         transcribe_result &r = out[b];
         r.tokens.assign(toks.begin() + (long)b * params.max_tokens, toks.begin() + (long)b * params.max_tokens + nt[b]);
-        if (params.token_logprobs)
+        if (want_lp)
             r.token_logprobs.assign(lps.begin() + (long)b * params.max_tokens, lps.begin() + (long)b * params.max_tokens + nt[b]);
         if (K > 0) {
             const long o = (long)b * params.max_tokens * K;
             r.alt_tokens.assign(alt_id.begin() + o, alt_id.begin() + o + (long)nt[b] * K);
             r.alt_logprobs.assign(alt_lp.begin() + o, alt_lp.begin() + o + (long)nt[b] * K);
         }
-        const int len = qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), nullptr, 0);
-        std::string text(std::max(len, 0) + 1, '\0');
-        qasr_detokenize(model_, r.tokens.data(), (int)r.tokens.size(), &text[0], (int)text.size());
-        text.resize(std::max(len, 0));
-        r.text = text;
+        auto detok = [&](const std::vector<int32_t> &t) {
+            const int len = qasr_detokenize(model_, t.data(), (int)t.size(), nullptr, 0);
+            std::string text(std::max(len, 0) + 1, '\0');
+            qasr_detokenize(model_, t.data(), (int)t.size(), &text[0], (int)text.size());
+            text.resize(std::max(len, 0));
+            return text;
+        };
+        r.text = detok(r.tokens);
+        if (beam) {
+            std::vector<int32_t> bt((size_t)W * params.max_tokens);
+            std::vector<int> bn(W), bf(W);
+            std::vector<float> bs(W);
+            const int nh = qasr_get_beams(ctx_, b, bt.data(), nullptr, bn.data(), bs.data(), bf.data(), W, params.max_tokens);
+            if (nh < 0) {
+                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+                continue;
+            }
+            for (int i = 0; i < nh; i++) {
+                beam_hypothesis h;
+                h.tokens.assign(bt.begin() + (long)i * params.max_tokens, bt.begin() + (long)i * params.max_tokens + bn[i]);
+                h.text = detok(h.tokens);
+                h.sum_logprob = bs[i];
+                h.finished = bf[i] != 0;
+                r.beams.push_back(std::move(h));
+            }
+        }
         r.success = true;
         r.t_mel_ms = (int64_t)tm.t_mel_ms;
         r.t_encode_ms = (int64_t)tm.t_encode_ms;
@@ -242,6 +278,15 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
 std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std::vector<float>> &clips,
                                                           const transcribe_params &params) {
     if (clips.size() <= 1) return transcribe_run(clips, params);
+    if (params.beam_width >= 2) {   // the stream has no beam search: whole runs of as many clips as max_batch() rows hold
+        std::vector<transcribe_result> out;
+        const size_t per = (size_t)std::max(1, max_batch_ / params.beam_width);
+        for (size_t i = 0; i < clips.size(); i += per) {
+            std::vector<std::vector<float>> part(clips.begin() + i, clips.begin() + std::min(clips.size(), i + per));
+            for (auto &r : transcribe_run(part, params)) out.push_back(std::move(r));
+        }
+        return out;
+    }
     if (!model_) return std::vector<transcribe_result>(clips.size(), [] { transcribe_result r; r.error_msg = "Model not loaded"; return r; }());
     std::vector<transcribe_result> out(clips.size());
     int maxP = 0;
@@ -327,7 +372,8 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     // chunking unit) plus the budget -- longer clips fail alone ("Context length")
     const int need = n_ctx > 0 ? n_ctx : qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(30 * 16000))) + (int)sys.size() + params.max_tokens;
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
-    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k)) return false;
+    if (params.beam_width >= 2) { error_msg_ = "The stream has no beam search (transcribe_params::beam_width)"; return false; }
+    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) || !set_beam_width(0)) return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};

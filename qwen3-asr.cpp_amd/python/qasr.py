@@ -36,6 +36,7 @@ EXPORTS = [
     "qasr_ctx_grow_shape",
     "qasr_get_step_logprobs", "qasr_get_logprobs", "qasr_stream_logprobs",
     "qasr_get_step_topk", "qasr_get_topk", "qasr_stream_topk",
+    "qasr_kv_fork", "qasr_get_beams", "qasr_prefill_slots",
 ]
 
 
@@ -60,6 +61,7 @@ class StreamStats(C.Structure):
                 ("t_encode_ms", C.c_double), ("kv_keys", C.c_int64)]
 
 
+QASR_BEAM_MAX = 8
 _lib = None
 # void (*)(void *user, int seq, int n_generated, int32_t token)
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int32)
@@ -117,6 +119,9 @@ def lib() -> C.CDLL:
             "qasr_stream_logprobs": ([P, F, I], I),
             "qasr_get_step_topk": ([P, I32P, F, I, I], I), "qasr_get_topk": ([P, I32P, F, I, I, I], I),
             "qasr_stream_topk": ([P, I32P, F, I, I], I),
+            "qasr_kv_fork": ([P, IP, IP, IP, I, I], I),
+            "qasr_get_beams": ([P, I, I32P, F, IP, F, IP, I, I], I),
+            "qasr_prefill_slots": ([P, I32P, IP, F, IP, IP, IP, I, F, I32P], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -297,6 +302,17 @@ class RunResult:
     # the K most likely tokens of every step (context option "top_k"): per row (ids [n][K] int32, logprobs [n][K]
     # float32), n the row's tokens and entry 0 of a step the token itself; None with the option off
     topk: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None
+    # every hypothesis of every clip of a beam run (context option "beam_width" >= 2), best first; tokens[b] is
+    # beams[b][0].tokens; None after a greedy run
+    beams: Optional[List[List["Beam"]]] = None
+
+
+@dataclass
+class Beam:
+    tokens: List[int]
+    logprobs: List[float]      # one per token (a popped EOS takes its value with it)
+    sum_logprob: float         # ... but the sum counts the EOS step
+    finished: bool
 
 
 def _sink_into(out: dict, failed: list, ctx=None, tk_ctx=None):
@@ -403,7 +419,8 @@ class Context:
     def encode_conv(self, mels):
         return self._encode(mels, True)
 
-    def prefill(self, ids_list, feats_list=None, audio_pos=None, want_logits=True):
+    def prefill(self, ids_list, feats_list=None, audio_pos=None, want_logits=True, slots=None):
+        """slots: sequence b's KV-cache slot (qasr_prefill_slots); None: slot b"""
         B = len(ids_list)
         P = np.array([len(x) for x in ids_list], np.int32)
         ids = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32) for x in ids_list]))
@@ -416,9 +433,33 @@ class Context:
         V = self.model.hp.vocab_size
         logits = np.zeros((B, V), np.float32) if want_logits else None
         am = np.zeros(B, np.int32)
+        if slots is not None:
+            sl = np.ascontiguousarray(slots, np.int32)
+            _check(lib().qasr_prefill_slots(self.h, _i32(ids), _i(P), _f(feats) if feats is not None else None, _i(ap), _i(N),
+                                            _i(sl), B, _f(logits) if want_logits else None, _i32(am)), "qasr_prefill_slots")
+            return logits, am
         _check(lib().qasr_prefill(self.h, _i32(ids), _i(P), _f(feats) if feats is not None else None, _i(ap), _i(N), B,
                                   _f(logits) if want_logits else None, _i32(am)), "qasr_prefill")
         return logits, am
+
+    def kv_fork(self, parent, frm, to, group: int) -> None:
+        """qasr_kv_fork: positions [frm[b], to[b]) of cache slot b take what slot parent[b] held (rows forked
+        inside groups of `group` consecutive rows)"""
+        par, f, t = (np.ascontiguousarray(x, np.int32) for x in (parent, frm, to))
+        _check(lib().qasr_kv_fork(self.h, _i(par), _i(f), _i(t), len(par), int(group)), "qasr_kv_fork")
+
+    def beams(self, clip: int) -> List[Beam]:
+        """qasr_get_beams: every hypothesis of clip `clip` of the last beam run, best first"""
+        W, T = QASR_BEAM_MAX, self.max_ctx
+        toks, lps = np.zeros((W, T), np.int32), np.zeros((W, T), np.float32)
+        nt, fin, sums = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(W, np.float32)
+        n = lib().qasr_get_beams(self.h, int(clip), _i32(toks), _f(lps), _i(nt), _f(sums), _i(fin), W, T)
+        if n < 0:
+            raise QasrError(f"qasr_get_beams: {lib().qasr_last_error().decode(errors='replace')}")
+        return [Beam(toks[i, :nt[i]].tolist(), lps[i, :nt[i]].tolist(), float(sums[i]), bool(fin[i])) for i in range(n)]
+
+    def _beam_on(self) -> bool:
+        return self.get_option("beam_width") >= 2 and not self.model.is_aligner
 
     def decode_step(self, tok, n_past, want_logits=True):
         tok = np.ascontiguousarray(tok, np.int32)
@@ -468,6 +509,8 @@ class Context:
         nt = np.zeros(B, np.int32)
         t = Timings()
         _check(lib().qasr_run(self.h, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)), "qasr_run")
+        if self._beam_on():
+            return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, beams=[self.beams(b) for b in range(B)])
         return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
                          self._run_topk(nt, max_tokens))
 
@@ -512,6 +555,8 @@ class Context:
         t = Timings()
         _check(lib().qasr_run_staged(self.h, _i(idx), B, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)),
                "qasr_run_staged")
+        if self._beam_on():
+            return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, beams=[self.beams(b) for b in range(B)])
         return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
                          self._run_topk(nt, max_tokens))
 
