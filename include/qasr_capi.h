@@ -48,6 +48,10 @@
  *       the KV-cache fork that lets a cache slot continue another slot's
  *       history, the hypotheses of the last beam run, and a prefill into
  *       chosen cache slots
+ *   qasr_prefill_score, qasr_score
+ *       no reference counterpart: teacher-forced scoring -- the log-probability
+ *       of every token of a transcript the caller brings, from an LM head
+ *       over many rows that never writes its logits
  *
  * Conventions (mirroring the reference's):
  *   - return value: 0 = OK, nonzero = error; message via qasr_last_error().
@@ -372,6 +376,51 @@ int qasr_get_beams(qasr_ctx *c, int clip, int32_t *tokens, float *logprobs, int 
 int qasr_prefill_slots(qasr_ctx *c, const int32_t *ids, const int *P, const float *feats, const int *audio_pos, const int *N,
                        const int *slots, int B, float *logits_last, int32_t *argmax);
 
+/* ---- teacher-forced scoring (no reference counterpart) ----------------------- */
+/* The log-probability the model gives a transcript the caller brings: for a scored row whose input
+ * is token t of a sequence and whose target is the token that follows it,
+ *   logprob = logit[target] - logsumexp(logits of the row, whole vocabulary)
+ * together with the row's greedy token (the argmax, ties to the lower id, as every greedy step) and
+ * that token's log-probability.  The LM head over the scored rows folds the log-sum-exp, the target's
+ * logit and the argmax into its GEMM epilogue (csrc/score_head.hip; DESIGN.md "Teacher-forced
+ * scoring"): no logits are written and nothing but three values a row reaches the host.  Results are
+ * bit-reproducible.  Neither call is captured or touches a step graph; options "token_logprobs",
+ * "top_k" and "beam_width" do not change their results.  ASR models only (aligner models:
+ * QASR_ERR_STATE).  Both return the number of values written (>= 0) or minus an error code.
+ *
+ * qasr_prefill_score (stage level): qasr_prefill / _chunk / _chunk_audio / _slots in one call --
+ *   n_past, feats (with audio_pos and N) and slots may each be NULL, with the meaning they have there
+ *   (n_past NULL: every sequence from position 0) -- plus targets[sum P_b]: the row of ids[t] is scored
+ *   against targets[t] (0 .. vocab - 1); targets[t] < 0: the row is not scored.  The outputs are
+ *   compacted in row order, one entry per scored row (cap >= their number, else QASR_ERR_ARG).  The
+ *   call also does everything the unscored call does (the last rows' argmax, the decode state).
+ *
+ * qasr_score (whole path, over the pool of qasr_stage_audio): sequence s is the hypothesis
+ *   tokens[off_s .. off_s + n_tokens[s]) (off_s = the sum of the earlier n_tokens) of staged clip
+ *   clips[s].  Entry k < n_tokens[s] of a sequence is the log-probability of its token k given the
+ *   clip's prompt and its tokens 0 .. k - 1; with include_eos != 0 one more entry scores the EOS token
+ *   after the last one.  Outputs: n_tokens[s] + (include_eos != 0) entries a sequence, back to back, in
+ *   input order (the caller sizes them so); sum_logprob [S] (optional): the float32 sum of each
+ *   sequence's entries in order.  The clips named need not be adjacent or sorted: mel, encoder and the
+ *   prompt's prefill run once per distinct clip, the prompt's KV rows are forked to the clip's other
+ *   hypotheses (qasr_kv_fork's kernel) and every hypothesis's tokens run as one chunk prefill in a
+ *   cache slot of their own.  A clip may have at most QASR_SCORE_MAX_HYP hypotheses a call; with D
+ *   distinct clips and G the largest number of hypotheses of one clip, D * G <= max_batch.
+ *   n_tokens[s] = 0 scores the EOS alone (include_eos) or yields nothing for that sequence.
+ *   Errors: null or short buffers, a token >= vocab, a clip index outside the pool, more than
+ *   QASR_SCORE_MAX_HYP hypotheses of one clip, D * G > max_batch, and prompt + n_tokens[s] + 1 > max_ctx
+ *   ("Context length exceeded") are QASR_ERR_ARG; no staged audio, an aligner model, and option
+ *   "fa_exact_prefill" = 0 (the chunk after cached tokens needs it) are QASR_ERR_STATE.
+ *   t (optional): t_decode_ms is the scoring after the prompts' prefill (fork, chunk prefill, heads).
+ *   After either call the decode state and, after qasr_score, the KV slots are unspecified: the next
+ *   decode starts from a prefill, as qasr_run* does. */
+#define QASR_SCORE_MAX_HYP 8
+int qasr_prefill_score(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, const float *feats,
+                       const int *audio_pos, const int *N, const int *slots, int B, const int32_t *targets,
+                       float *logprobs, int32_t *greedy_ids, float *greedy_logprobs, int cap);
+int qasr_score(qasr_ctx *c, const int *clips, const int32_t *tokens, const int *n_tokens, int S, int include_eos,
+               float *logprobs, int32_t *greedy_ids, float *greedy_logprobs, float *sum_logprob, qasr_timings *t);
+
 /* Per-token callback (Qwen3ASR::set_progress_callback, src/qwen3_asr.cpp:255-291):
  * called synchronously on the caller's thread after every greedy token of
  * qasr_run / qasr_run_staged -- the prefill's token first (n_generated = 1) --
@@ -590,6 +639,26 @@ typedef struct {
     int32_t declined;
 } qasr_kt_beam_select_args;
 int qasr_kt_beam_select(int device, qasr_kt_beam_select_args *a);
+
+/* launch_score_head on caller-supplied arrays (csrc/score_head.hip), `launches` (>= 1) times on the same
+ * device state.  In, each with `guard` rows of 0xFF after its last row: A fp16 [R][lda], W fp16 [N][ldw],
+ * target [R].  Out, each [R + 2 guard] with the guard entries 0xFF before the launch: lp, gid, glp.  The
+ * scratch is filled with 0xFF bytes before the first launch. */
+typedef struct {
+    int32_t R, N, K, lda, ldw, n_valid;
+    int32_t cols_fast;       /* ScoreHeadArgs::cols_fast */
+    int32_t guard, launches;
+    const uint16_t *A;
+    const uint16_t *W;
+    const int32_t *target;
+    float *lp;
+    int32_t *gid;
+    float *glp;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_score_args;
+int qasr_kt_score_head(int device, qasr_kt_score_args *a);
 
 #ifdef __cplusplus
 }

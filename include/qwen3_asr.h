@@ -71,6 +71,18 @@ struct transcribe_result {
     std::vector<beam_hypothesis> beams;
 };
 
+// MI355X addition (trailing): one text scored as a transcript of a clip (Qwen3ASR::score) -- the
+// log-probability the model gives every token of the text, and the EOS after it, given the audio
+struct score_result {
+    std::vector<int32_t> tokens;          // the text's ids, then the EOS
+    std::vector<float> token_logprobs;    // log softmax(logits)[token], one per entry of tokens
+    std::vector<int32_t> greedy_tokens;   // the model's own argmax at each position
+    std::vector<float> greedy_logprobs;   // ... and its log-probability
+    float sum_logprob = 0.f;              // float32 sum of token_logprobs, in order
+    bool success = false;
+    std::string error_msg;
+};
+
 using progress_callback_t = std::function<void(int tokens_generated, int max_tokens)>;
 
 // src/qwen3_asr.h:55-116
@@ -114,6 +126,12 @@ public:
     const std::string &profile_report() const { return profile_report_; }
     // the text of one token id (empty without a model): for listing transcribe_result::alt_tokens
     std::string token_text(int32_t id) const;
+    // teacher-forced scoring (qasr_score of qasr_capi.h; no reference counterpart): each text goes through
+    // the model's tokenizer verbatim, the EOS is appended and scored; params.system_prompt is honoured, the
+    // other fields are not used.  The clip's mel, encoder and prompt prefill run once per group of at most
+    // 8 texts; results in input order, each text's success / error_msg its own
+    std::vector<score_result> score(const float *samples, int n_samples, const std::vector<std::string> &texts,
+                                    const transcribe_params &params = transcribe_params());
 
 private:
     transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params);

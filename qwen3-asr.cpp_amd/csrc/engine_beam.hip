@@ -8,7 +8,7 @@ using namespace qasr;
 using namespace qasr::eng;
 
 // ------------------------------------------------------------------- fork
-static KvForkArgs fork_args(qasr_ctx *c, const int *parent, const int *from, const int *to, int B, int group, int blocks) {
+KvForkArgs qasr::eng::fork_args(qasr_ctx *c, const int *parent, const int *from, const int *to, int B, int group, int blocks) {
     KvForkArgs a{};
     a.kc = c->kc; a.vc = c->vc; a.vt = c->vt;
     a.layers = c->m->hp.dec_layers; a.n_kv_head = c->m->hp.n_kv_head; a.max_ctx = c->max_ctx; a.slots = c->max_batch;

@@ -7,6 +7,7 @@
 //   engine_decode.hip  the decode-step emitter, graph capture, kernel probes, qasr_decode_step
 //   engine_run.hip     qasr_run, the continuous-batching stream, their log-probability readers
 //   engine_beam.hip    beam search: the KV-cache fork entry, the beam loop, the hypothesis reader
+//   engine_score.hip   teacher-forced scoring: the score head over prefill rows, qasr_prefill_score, qasr_score
 //   engine_align.hip   the forced aligner and its JSON output
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include "../host/gguf.h"
 #include "../host/qasr_host.h"
 #include "beam_host.h"
+#include "score_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -189,6 +191,9 @@ struct qasr_ctx {
     bool last_run_beam = false;        // the last qasr_run was a beam run (qasr_get_logprobs / qasr_get_topk refuse)
     std::vector<std::vector<qasr::BeamHyp>> beam_res;   // its hypotheses per clip, best first
     DevBuf fork_args;                  // qasr_kv_fork: the caller's parent | from | to on the device
+    // teacher-forced scoring (engine_score.hip): the gathered normed rows (fp16), row indices | targets, the three
+    // outputs of a block of rows, the score head's scratch
+    DevBuf sc_rows, sc_tab, sc_out, sc_scratch;
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -321,6 +326,9 @@ int prefill_layers(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vect
 int run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const std::vector<int> &P, const float *d_feats,
                 const std::vector<int> &audio_pos, const std::vector<int> &N, bool want_logits,
                 const std::vector<int> *slots = nullptr, const std::vector<int> *pos0 = nullptr);
+// the body of qasr_prefill / _chunk / _chunk_audio / _slots (n_past, feats, slots: null as there)
+int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, const float *feats, const int *audio_pos,
+                         const int *N, int B, float *logits_last, int32_t *argmax, const int *slots = nullptr);
 
 // a roctx range for the lifetime of the object (rocprofv3 --marker-trace); engine_run.hip
 struct RoctxRange {
@@ -338,6 +346,7 @@ int front_end_staged(qasr_ctx *c, int max_tokens, const std::vector<int> *slots,
 int run_timings(qasr_ctx *c, int steps, qasr_timings *t);
 
 // engine_beam.hip
+KvForkArgs fork_args(qasr_ctx *c, const int *parent, const int *from, const int *to, int B, int group, int blocks);
 int beam_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
 // the beam step and the fork that end a decode step of a beam run (blocks: 8-key blocks the fork's grid covers)
 int beam_step(qasr_ctx *c, int G, int blocks);

@@ -603,9 +603,9 @@ extern "C" int qasr_encoder_frames_no_chunk(int n_mel_frames) {
 // n_past == nullptr is qasr_prefill: every sequence from position 0, with the
 // plain prefill's attention arguments (no seq_pos0) and its laxer argument rules.
 // slots (qasr_prefill_slots): sequence b's KV-cache slot; nullptr = slot b
-static int prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, const float *feats,
-                                const int *audio_pos, const int *N, int B, float *logits_last, int32_t *argmax,
-                                const int *slots = nullptr) {
+int qasr::eng::prefill_chunk_common(qasr_ctx *c, const int32_t *ids, const int *P, const int *n_past, const float *feats,
+                                    const int *audio_pos, const int *N, int B, float *logits_last, int32_t *argmax,
+                                    const int *slots) {
     if (!c || !ids || !P || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     if (n_past) {
         if (feats && (!N || !audio_pos)) return fail(QASR_ERR_ARG, "audio features need N and audio_pos");

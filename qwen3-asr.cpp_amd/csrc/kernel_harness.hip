@@ -324,3 +324,38 @@ extern "C" int qasr_kt_beam_select(int device, qasr_kt_beam_select_args *a) {
         return rc;
     return 0;
 }
+
+// --------------------------------------------------------------- score head
+extern "C" int qasr_kt_score_head(int device, qasr_kt_score_args *a) {
+    if (!a || a->R <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || !a->A || !a->W || !a->target || !a->lp ||
+        !a->gid || !a->glp)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    if (a->lda < a->K || a->ldw < a->K) return fail(QASR_ERR_ARG, "leading dimensions smaller than the rows");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int R = a->R, G = a->guard;
+    KtBuf A, W, tg, lp, gid, glp, scr;
+    if ((rc = put_in(A, a->A, R, a->lda, 2, G, 0xFF)) || (rc = put_in(W, a->W, a->N, a->ldw, 2, G, 0xFF)) ||
+        (rc = put_in(tg, a->target, R, 1, 4, G, 0xFF)) || (rc = put_out(lp, a->lp, R, 1, 4, G)) ||
+        (rc = put_out(gid, a->gid, R, 1, 4, G)) || (rc = put_out(glp, a->glp, R, 1, 4, G)))
+        return rc;
+    scr.bytes = std::max<size_t>(score_head_scratch(R, a->N), 256);
+    HIPCHK(hipMalloc((void **)&scr.d, scr.bytes));
+    HIPCHK(hipMemset(scr.d, 0xFF, scr.bytes));
+    ScoreHeadArgs s{};
+    s.A = A.ptr<uint16_t>(); s.lda = a->lda;
+    s.W = W.ptr<uint16_t>(); s.ldw = a->ldw;
+    s.R = R; s.N = a->N; s.K = a->K; s.n_valid = a->n_valid;
+    s.target = tg.ptr<int32_t>();
+    s.lp = lp.ptr<float>(); s.gid = gid.ptr<int32_t>(); s.glp = glp.ptr<float>();
+    s.scratch = scr.d;
+    s.cols_fast = a->cols_fast;
+    bool ran = true;
+    for (int i = 0; i < a->launches && ran; i++) {
+        ran = launch_score_head(s, nullptr);
+        if (ran && i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
+    }
+    if ((rc = finish(a, ran))) return rc;
+    if ((rc = get(lp, a->lp)) || (rc = get(gid, a->gid)) || (rc = get(glp, a->glp))) return rc;
+    return 0;
+}

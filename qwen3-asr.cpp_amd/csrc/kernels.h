@@ -131,6 +131,27 @@ void launch_gemm_q8(int epi, const GemmArgs &g, hipStream_t s);
 void launch_quantize_q8(const float *x32, const uint16_t *x16, int ldx, int M, int K, int gather_C, int8_t *q, float *d,
                         hipStream_t s);
 
+// score_head.hip: teacher-forced scoring of R rows against one target id each, the log-sum-exp, the
+// target's logit and the row argmax folded into the GEMM epilogue (no R x N buffer exists):
+//   lp[r] = logit[r][target[r]] - logsumexp(logit[r][0 .. n_valid)), gid[r] = the row's argmax in
+//   argmax_key order, glp[r] = that token's log-probability (lse_logprob)
+// Shapes taken: R >= 1, N % 128 == 0, K % 128 == 0, lda / ldw >= K and % 8 == 0.  Two launches on the
+// stream (tiles, then a per-row merge of the column-tile partials in a fixed order); bit-reproducible.
+struct ScoreHeadArgs {
+    const uint16_t *A; int lda;      // fp16 [R][lda]: the normed hidden rows
+    const uint16_t *W; int ldw;      // fp16 [N][ldw]: token_embd
+    int R, N, K, n_valid;            // n_valid: columns >= n_valid enter neither the sum nor the argmax; 0 = N
+    const int32_t *target;           // [R]: 0 .. n_valid - 1
+    float *lp;                       // [R]
+    int32_t *gid;                    // [R]
+    float *glp;                      // [R]
+    void *scratch;                   // score_head_scratch(R, N) bytes, 256-byte aligned, owned by the caller
+    int cols_fast;                   // diagnostic: 1 = column tiles on the fast grid axis (default 0: row tiles,
+                                     // the workgroups sharing a slice of W run together)
+};
+size_t score_head_scratch(int R, int N);
+bool launch_score_head(const ScoreHeadArgs &a, hipStream_t s);   // false = shape not taken, nothing launched
+
 // skinny (decode) path: M <= 8 rows, weights streamed once from HBM.
 // x is fp32 [M][K]; if norm_w != nullptr the rows are RMS-normalised first
 // (ggml_rms_norm + ggml_mul), then rounded to fp16 as ggml's mul_mat does.

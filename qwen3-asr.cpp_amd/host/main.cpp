@@ -36,6 +36,7 @@ struct cli_params {
     int32_t top_k = 0;       // --top-k: alternatives per token (transcribe_params::top_k)
     int32_t beam_width = 0;  // --beam-width: beam search of this width (transcribe_params::beam_width)
     bool beams = false;      // --beams: list every hypothesis of a beam run
+    std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
 };
 
@@ -54,6 +55,12 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
     fprintf(stderr, "  --beam-width <n>       Beam search of width n (2..8) instead of greedy decoding\n");
     fprintf(stderr, "  --beams                With --beam-width: list every hypothesis with its summed log-probability\n");
+    fprintf(stderr, "  --score <text>         Score <text> as a transcript of the -f file instead of transcribing (repeatable):\n");
+    fprintf(stderr, "                         per text the summed log-probability, the mean per token and the token count\n");
+    fprintf(stderr, "                         (the EOS included); with --tokens every token's id, text and log-probability,\n");
+    fprintf(stderr, "                         and the model's own greedy token where it differs.  The text is scored as\n");
+    fprintf(stderr, "                         given: the real model's reply carries its 'language ...<asr_text>' prefix,\n");
+    fprintf(stderr, "                         so a text without it is scored as a reply that lacks it\n");
     fprintf(stderr, "  --profile              Print timing profile\n");
     fprintf(stderr, "  --device <n>           HIP device index (default: 0)\n");
     fprintf(stderr, "  --file-list <path>     Text file with one audio path per line (added to the -f files)\n");
@@ -120,6 +127,7 @@ static bool parse(int argc, char **argv, cli_params &p) {
             if (p.beam_width < 2 || p.beam_width > 8) { fprintf(stderr, "Error: --beam-width takes 2..8\n"); return false; }
         }
         else if (!strcmp(a, "--beams")) p.beams = true;
+        else if (!strcmp(a, "--score")) { if (!val(v)) return false; p.score_texts.push_back(v); }
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
         else if (!strcmp(a, "-a") || !strcmp(a, "--transcribe-align")) p.transcribe_align_mode = true;
@@ -130,6 +138,10 @@ static bool parse(int argc, char **argv, cli_params &p) {
     }
     if (!p.synthetic.empty()) return true;
     if (p.audio_paths.empty()) { fprintf(stderr, "Error: Audio file path is required (-f/--audio)\n"); return false; }
+    if (!p.score_texts.empty() && (p.audio_paths.size() != 1 || p.align_mode || p.transcribe_align_mode || !p.devices.empty())) {
+        fprintf(stderr, "Error: --score takes one -f file and no alignment or --devices\n");
+        return false;
+    }
     // src/main.cpp:76-90
     if (p.align_mode && p.align_text.empty()) {
         fprintf(stderr, "Error: Reference text is required for alignment mode (--text)\n");
@@ -475,6 +487,35 @@ static int run_transcription(const cli_params &p) {
     return rc;
 }
 
+// --score: every text as a transcript of the one audio file, one line per text on the output
+static int run_scoring(const cli_params &p) {
+    qwen3_asr::Qwen3ASR asr;
+    asr.set_device(p.device);
+    if (!asr.load_model(p.model_path)) { fprintf(stderr, "Error: %s\n", asr.get_error().c_str()); return 1; }
+    std::vector<float> pcm;
+    int sr = 0;
+    if (!qwen3_asr::load_audio_file(p.audio_paths[0], pcm, sr) || sr != 16000) { fprintf(stderr, "Error: bad audio %s\n", p.audio_paths[0].c_str()); return 1; }
+    const std::vector<qwen3_asr::score_result> rs = asr.score(pcm.data(), (int)pcm.size(), p.score_texts);
+    std::string all;
+    for (size_t i = 0; i < rs.size(); i++) {
+        const qwen3_asr::score_result &r = rs[i];
+        if (!r.success) { fprintf(stderr, "Error: %s\n", r.error_msg.c_str()); return 1; }
+        char line[160];
+        snprintf(line, sizeof line, "%.4f\t%.4f\t%zu\t", r.sum_logprob, r.sum_logprob / (float)r.tokens.size(), r.tokens.size());
+        all += line + p.score_texts[i] + "\n";
+        if (p.print_tokens) {
+            fprintf(stderr, "\nScore [%zu] \"%s\" (%zu tokens):\n", i, p.score_texts[i].c_str(), r.tokens.size());
+            for (size_t k = 0; k < r.tokens.size(); ++k) {
+                fprintf(stderr, "  [%zu] %d \"%s\" %.4f", k, r.tokens[k], asr.token_text(r.tokens[k]).c_str(), r.token_logprobs[k]);
+                if (r.greedy_tokens[k] != r.tokens[k])
+                    fprintf(stderr, "   (greedy %d \"%s\" %.4f)", r.greedy_tokens[k], asr.token_text(r.greedy_tokens[k]).c_str(), r.greedy_logprobs[k]);
+                fprintf(stderr, "\n");
+            }
+        }
+    }
+    return write_output(p, all);
+}
+
 int main(int argc, char **argv) {
     cli_params p;
     if (!parse(argc, argv, p)) { fprintf(stderr, "\n"); usage(argv[0]); return 1; }
@@ -489,5 +530,6 @@ int main(int argc, char **argv) {
     if (p.transcribe_align_mode) return run_transcribe_and_align(p);
     if (p.align_mode) return run_alignment(p);
     if (!p.devices.empty()) return run_transcription_sharded(p);
+    if (!p.score_texts.empty()) return run_scoring(p);
     return run_transcription(p);
 }

@@ -417,6 +417,66 @@ std::string Qwen3ASR::token_text(int32_t id) const {
     return text;
 }
 
+std::vector<score_result> Qwen3ASR::score(const float *samples, int n_samples, const std::vector<std::string> &texts,
+                                          const transcribe_params &params) {
+    std::vector<score_result> out(texts.size());
+    auto fail_all = [&](const std::string &msg) {
+        for (auto &r : out)
+            if (!r.success) r.error_msg = msg;
+        return out;
+    };
+    if (!model_) return fail_all("Model not loaded");
+    if (texts.empty()) return out;
+    std::vector<int32_t> sys;
+    if (!params.system_prompt.empty()) {
+        const int k = qasr_tokenize(model_, params.system_prompt.c_str(), nullptr, 0);
+        sys.resize(std::max(k, 0));
+        qasr_tokenize(model_, params.system_prompt.c_str(), sys.data(), k);
+    }
+    int longest = 0;
+    for (size_t i = 0; i < texts.size(); i++) {
+        const int k = std::max(qasr_tokenize(model_, texts[i].c_str(), nullptr, 0), 0);
+        out[i].tokens.resize(k);
+        qasr_tokenize(model_, texts[i].c_str(), out[i].tokens.data(), k);
+        longest = std::max(longest, k);
+    }
+    const int P = qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(n_samples))) + (int)sys.size();
+    const int per = std::min<int>(QASR_SCORE_MAX_HYP, (int)texts.size());
+    if (!ensure_ctx(per, P + longest + 1)) return fail_all(error_msg_);
+    qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
+    if (qasr_stage_audio(ctx_, &samples, &n_samples, 1) != 0) return fail_all(std::string("Scoring failed: ") + qasr_last_error());
+    for (size_t i0 = 0; i0 < texts.size(); i0 += per) {   // more than 8 texts: in groups
+        const int S = (int)std::min<size_t>(per, texts.size() - i0);
+        std::vector<int> clips(S, 0), nt(S);
+        std::vector<int32_t> toks;
+        for (int s = 0; s < S; s++) {
+            nt[s] = (int)out[i0 + s].tokens.size();
+            toks.insert(toks.end(), out[i0 + s].tokens.begin(), out[i0 + s].tokens.end());
+        }
+        const size_t total = toks.size() + S;
+        std::vector<float> lp(total), glp(total), sums(S);
+        std::vector<int32_t> gid(total);
+        const int rc = qasr_score(ctx_, clips.data(), toks.data(), nt.data(), S, 1, lp.data(), gid.data(), glp.data(), sums.data(), nullptr);
+        size_t o = 0;
+        for (int s = 0; s < S; s++) {
+            score_result &r = out[i0 + s];
+            const size_t k = (size_t)nt[s] + 1;
+            if (rc < 0) {
+                r.error_msg = std::string("Scoring failed: ") + qasr_last_error();
+            } else {
+                r.tokens.push_back(config_.eos_token_id);
+                r.token_logprobs.assign(lp.begin() + o, lp.begin() + o + k);
+                r.greedy_tokens.assign(gid.begin() + o, gid.begin() + o + k);
+                r.greedy_logprobs.assign(glp.begin() + o, glp.begin() + o + k);
+                r.sum_logprob = sums[s];
+                r.success = true;
+            }
+            o += k;
+        }
+    }
+    return out;
+}
+
 void Qwen3ASR::set_progress_callback(progress_callback_t callback) { progress_callback_ = std::move(callback); }
 
 bool load_audio_file(const std::string &path, std::vector<float> &samples, int &sample_rate) {

@@ -37,6 +37,7 @@ EXPORTS = [
     "qasr_get_step_logprobs", "qasr_get_logprobs", "qasr_stream_logprobs",
     "qasr_get_step_topk", "qasr_get_topk", "qasr_stream_topk",
     "qasr_kv_fork", "qasr_get_beams", "qasr_prefill_slots",
+    "qasr_prefill_score", "qasr_score",
 ]
 
 
@@ -122,6 +123,8 @@ def lib() -> C.CDLL:
             "qasr_kv_fork": ([P, IP, IP, IP, I, I], I),
             "qasr_get_beams": ([P, I, I32P, F, IP, F, IP, I, I], I),
             "qasr_prefill_slots": ([P, I32P, IP, F, IP, IP, IP, I, F, I32P], I),
+            "qasr_prefill_score": ([P, I32P, IP, IP, F, IP, IP, IP, I, I32P, F, I32P, F, I], I),
+            "qasr_score": ([P, IP, I32P, IP, I, I, F, I32P, F, F, C.POINTER(Timings)], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -315,6 +318,16 @@ class Beam:
     finished: bool
 
 
+@dataclass
+class Score:
+    """one scored sequence (Context.score / Context.prefill_score): per scored position the log-probability
+    of the given token, the model's own greedy token there and that token's log-probability"""
+    logprobs: np.ndarray         # float32 [n]
+    greedy_ids: np.ndarray       # int32 [n]
+    greedy_logprobs: np.ndarray  # float32 [n]
+    sum: float                   # float32 sum of logprobs, in order
+
+
 def _sink_into(out: dict, failed: list, ctx=None, tk_ctx=None):
     """ctx: the running context when the caller asked for log-probabilities --
     the sink then stores (tokens, logprobs) per clip (qasr_stream_logprobs);
@@ -441,6 +454,65 @@ class Context:
         _check(lib().qasr_prefill(self.h, _i32(ids), _i(P), _f(feats) if feats is not None else None, _i(ap), _i(N), B,
                                   _f(logits) if want_logits else None, _i32(am)), "qasr_prefill")
         return logits, am
+
+    def prefill_score(self, ids_list, targets_list, n_past=None, feats_list=None, audio_pos=None, slots=None) -> List["Score"]:
+        """qasr_prefill_score: the prefill of ids_list (n_past / feats_list + audio_pos / slots as in prefill,
+        prefill_chunk and prefill(slots=...); None as there) with the row of ids_list[b][t] scored against
+        targets_list[b][t] (< 0: not scored).  One Score per sequence over its scored rows, in order."""
+        B = len(ids_list)
+        P = np.array([len(x) for x in ids_list], np.int32)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32) for x in ids_list]), np.int32)
+        tg = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32) for x in targets_list]), np.int32)
+        if len(tg) != len(ids) or any(len(t) != len(x) for t, x in zip(targets_list, ids_list)):
+            raise ValueError("targets_list must have the shape of ids_list")
+        npast = None if n_past is None else np.ascontiguousarray(n_past, np.int32)
+        sl = None if slots is None else np.ascontiguousarray(slots, np.int32)
+        feats, N, ap = None, None, None
+        if feats_list is not None:
+            N = np.array([f.shape[0] for f in feats_list], np.int32)
+            feats = np.ascontiguousarray(np.concatenate([np.asarray(f, np.float32) for f in feats_list]))
+            ap = np.ascontiguousarray(audio_pos, np.int32)
+        cap = max(int((tg >= 0).sum()), 1)
+        lp, gid, glp = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+        n = lib().qasr_prefill_score(self.h, _i32(ids), _i(P), _i(npast) if npast is not None else None,
+                                     _f(feats) if feats is not None else None, _i(ap) if ap is not None else None,
+                                     _i(N) if N is not None else None, _i(sl) if sl is not None else None, B, _i32(tg),
+                                     _f(lp), _i32(gid), _f(glp), cap)
+        if n < 0:
+            raise QasrError(f"qasr_prefill_score: {lib().qasr_last_error().decode(errors='replace')}")
+        res, o = [], 0
+        for t in targets_list:
+            k = int((np.asarray(t) >= 0).sum())
+            res.append(Score(lp[o:o + k].copy(), gid[o:o + k].copy(), glp[o:o + k].copy(),
+                             float(np.cumsum(lp[o:o + k], dtype=np.float32)[-1]) if k else 0.0))   # (in order, as qasr_score)
+            o += k
+        return res
+
+    def score(self, clips: Sequence[int], hyps, include_eos: bool = True, timings: Optional["Timings"] = None) -> List["Score"]:
+        """qasr_score: hyps[s] (token ids) scored as a transcript of staged clip clips[s] (stage_audio); one
+        Score per sequence with len(hyps[s]) + include_eos entries.  Hypotheses of one clip (at most 8 a call,
+        anywhere in the list) share the clip's mel, encoder and prompt prefill."""
+        idx = np.ascontiguousarray(clips, np.int32)
+        S = len(idx)
+        if len(hyps) != S:
+            raise ValueError("one hypothesis per clip index")
+        nt = np.array([len(h) for h in hyps], np.int32)
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(h, np.int32).reshape(-1) for h in hyps] + [np.zeros(0, np.int32)]), np.int32)
+        e = 1 if include_eos else 0
+        total = int(nt.sum()) + e * S
+        lp, gid, glp = (np.zeros(max(total, 1), np.float32), np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.float32))
+        sums = np.zeros(max(S, 1), np.float32)
+        t = timings if timings is not None else Timings()
+        n = lib().qasr_score(self.h, _i(idx), _i32(toks) if len(toks) else None, _i(nt), S, e, _f(lp), _i32(gid), _f(glp), _f(sums),
+                             C.byref(t))
+        if n < 0:
+            raise QasrError(f"qasr_score: {lib().qasr_last_error().decode(errors='replace')}")
+        res, o = [], 0
+        for s in range(S):
+            k = int(nt[s]) + e
+            res.append(Score(lp[o:o + k].copy(), gid[o:o + k].copy(), glp[o:o + k].copy(), float(sums[s])))
+            o += k
+        return res
 
     def kv_fork(self, parent, frm, to, group: int) -> None:
         """qasr_kv_fork: positions [frm[b], to[b]) of cache slot b take what slot parent[b] held (rows forked
