@@ -660,6 +660,66 @@ typedef struct {
 } qasr_kt_score_args;
 int qasr_kt_score_head(int device, qasr_kt_score_args *a);
 
+/* ---- temperature sampling with n-best ---------------------- */
+/* With sampling on, every token a prefill or decode step yields is drawn on the device from
+ * softmax(logits / temperature) restricted to the tokens whose probability is at least min_p times the
+ * greedy token's (seeded Gumbel-max; the rule is normative, DESIGN.md §5.5 and tests/sample_util.py).  A
+ * draw is identified by (seed, clip, sample, t) and depends on nothing else: not on its row, its batch or
+ * the grid.  clip = the staged pool index in qasr_run / qasr_run_staged, sample = 0 .. n_best - 1, t = the
+ * token's index within its hypothesis (0 = drawn from the prefill's logits).
+ * temperature in (0, 100], min_p in [0, 1], n_best in 1 .. QASR_SAMPLE_MAX, else QASR_ERR_ARG; NULL or
+ * temperature <= 0 turns sampling off (nothing of the greedy paths changes).  Changing temperature, min_p
+ * or seed re-captures no step graph.  While sampling is on, qasr_run_stream* and option beam_width >= 2
+ * are refused with QASR_ERR_STATE; aligner models ignore it; qasr_score / qasr_prefill_score are unaffected.
+ * Log-probabilities (option token_logprobs, qasr_get_samples) are log softmax(logits)[token] at T = 1, the
+ * model's own value; option top_k is unchanged (entry 0 stays the greedy token, which need not be the drawn one). */
+#define QASR_SAMPLE_MAX 8
+typedef struct {
+    float temperature, min_p;
+    uint64_t seed;
+    int32_t n_best;
+} qasr_sampling;
+int qasr_set_sampling(qasr_ctx *c, const qasr_sampling *s);
+int qasr_get_sampling(const qasr_ctx *c, qasr_sampling *out);
+/* Stage level: the identities rows 0 .. B - 1 of qasr_prefill* / qasr_decode_step draw with, t advancing by
+ * one per draw (n_best plays no part there; their `argmax` output then carries the drawn token).  A context
+ * starts with row b = (clip b, sample 0, t 0).  QASR_ERR_STATE while sampling is off. */
+int qasr_set_sample_streams(qasr_ctx *c, const int32_t *clip, const int32_t *sample, const int32_t *t, int B);
+/* The n_best hypotheses of clip `clip` (index into the run's clips) of the last sampling qasr_run, in sample
+ * order: tokens / logprobs [cap_hyp][max_tokens] (logprobs may be NULL), n_tokens / sum_logprob [cap_hyp].
+ * A trailing EOS is popped from the tokens and log-probabilities but counted in the fp32 in-order sum, as
+ * in qasr_get_beams.  The run's own tokens / n_tokens are sample 0's.  After an n_best >= 2 run
+ * qasr_get_logprobs / qasr_get_topk return QASR_ERR_STATE.  Returns the count, or minus an error code
+ * (QASR_ERR_STATE after a run with sampling off). */
+int qasr_get_samples(qasr_ctx *c, int clip, int32_t *tokens, float *logprobs, int *n_tokens, float *sum_logprob, int cap_hyp,
+                     int max_tokens);
+
+/* test only: launch_sample (csrc/sample.hip) on caller-supplied arrays, `launches` (>= 1) times; t is uploaded
+ * again before every launch, so repeated launches draw the same tokens.  In: logits [R / src_div][ld] with
+ * `guard` rows of 0xFF after the last row, greedy [R / src_div] (each inside [0, n_valid)), clip / sample / t
+ * [R].  Out, each [R + 2 guard] with the guard entries 0xFF before the launch: tok, key (the winning fp32 key),
+ * hist (one history slot).  t_out [R]: t after the last launch; skey_out [R]: the key scratch after it (zero
+ * at rest; it lies between two 4 KiB fences of 0xFF the launch must leave alone).  slices: 0 = the
+ * launcher's choice.  dump_n > 0: no draw; dump [dump_n] = G(u_n) for n = dump_n0 .. dump_n0 + dump_n - 1
+ * (n < 2^23), the device's value of the rule's steps 2 and 3. */
+typedef struct {
+    int32_t R, ld, n_valid, src_div, slices, guard, launches;
+    float inv_T, cut;
+    uint64_t seed;
+    const float *logits;
+    const int32_t *greedy, *clip, *sample, *t;
+    int32_t *tok;
+    float *key;
+    int32_t *hist, *t_out;
+    uint64_t *skey_out;
+    uint32_t dump_n0, dump_n;
+    float *dump;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_sample_args;
+int qasr_kt_sample(int device, qasr_kt_sample_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,15 @@ struct transcribe_params {
     // reports no per-token progress and fills neither token_logprobs nor alt_tokens: its values are in
     // transcribe_result::beams
     int32_t beam_width = 0;
+    // MI355X addition (trailing, default off): temperature sampling (qasr_set_sampling of qasr_capi.h; no reference
+    // counterpart).  temperature > 0 draws every token from softmax(logits / temperature) among the tokens at least
+    // min_p times as probable as the greedy one, seeded; n_best (1..8) hypotheses a clip, in
+    // transcribe_result::samples.  Excludes beam_width >= 2; n_best >= 2 reports no per-token progress and fills
+    // neither token_logprobs nor alt_tokens
+    float temperature = 0.f;
+    float min_p = 0.f;
+    uint64_t seed = 0;
+    int32_t n_best = 1;
 };
 
 // MI355X addition: one hypothesis of a beam run
@@ -45,6 +54,14 @@ struct beam_hypothesis {
     std::string text;
     float sum_logprob = 0.f;       // the EOS step included
     bool finished = false;         // ended in EOS (else the token budget ran out)
+};
+
+// MI355X addition: one hypothesis of a sampling run
+struct sample_hypothesis {
+    std::vector<int32_t> tokens;          // a trailing EOS popped
+    std::string text;
+    std::vector<float> token_logprobs;    // log softmax(logits)[token] at T = 1, one per token
+    float sum_logprob = 0.f;              // the EOS step included
 };
 
 // src/qwen3_asr.h:37-49
@@ -69,6 +86,9 @@ struct transcribe_result {
     // MI355X addition (trailing): with transcribe_params::beam_width >= 2, every hypothesis of the clip,
     // best first (tokens / text above are beams[0]'s); empty otherwise
     std::vector<beam_hypothesis> beams;
+    // MI355X addition (trailing): with transcribe_params::temperature > 0, the clip's n_best hypotheses in sample
+    // order (tokens / text above are samples[0]'s); empty otherwise
+    std::vector<sample_hypothesis> samples;
 };
 
 // MI355X addition (trailing): one text scored as a transcript of a clip (Qwen3ASR::score) -- the
@@ -139,6 +159,7 @@ private:
     bool set_logprobs(bool on);
     bool set_top_k(int k);
     bool set_beam_width(int w);
+    bool set_sampling(const transcribe_params &params);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

@@ -247,13 +247,15 @@ void launch_argmax_finish(const unsigned long long *amax, int B, int32_t *ids, i
 // into its own (m, s) pair (dev_common.h lse_add), the wave's 64 pairs merge by
 // xor-shuffles (32 .. 1), the 16 wave pairs through LDS in wave order: a fixed
 // order, so a row's value depends on its logits alone.
+// MAP: row b reads logits row b / src_div (the plain instance is the kernel as it was)
+template <bool MAP>
 __global__ __launch_bounds__(1024) void token_logprob_kernel(const float *__restrict__ logits, int ld, int n_valid,
                                                               const int32_t *__restrict__ tok, const int *__restrict__ step,
                                                               float *__restrict__ lp_out, float *__restrict__ lp_hist,
-                                                              int hist_stride) {
+                                                              int hist_stride, int src_div) {
     __shared__ float wm[16], ws[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const float *row = logits + (long)b * ld;
+    const float *row = logits + (long)(MAP ? b / src_div : b) * ld;
     float m = -INFINITY, s = 0.f;
     const int n4 = (ld & 3) ? 0 : n_valid >> 2;   // float4 columns (rows 16-B aligned), then the tail
     for (int i = tid; i < n4; i += 1024) {
@@ -278,10 +280,15 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const float *__rest
 }
 
 void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const int32_t *tok, const int *step, float *lp_out,
-                          float *lp_hist, int hist_stride, hipStream_t s) {
+                          float *lp_hist, int hist_stride, hipStream_t s, int src_div) {
     if (B <= 0) return;
-    hipLaunchKernelGGL(token_logprob_kernel, dim3(B), dim3(1024), 0, s, logits, ld, n_valid > 0 && n_valid < ld ? n_valid : ld,
-                       tok, step, lp_out, lp_hist, hist_stride);
+    const int nv = n_valid > 0 && n_valid < ld ? n_valid : ld;
+    if (src_div > 1)
+        hipLaunchKernelGGL(token_logprob_kernel<true>, dim3(B), dim3(1024), 0, s, logits, ld, nv, tok, step, lp_out, lp_hist,
+                           hist_stride, src_div);
+    else
+        hipLaunchKernelGGL(token_logprob_kernel<false>, dim3(B), dim3(1024), 0, s, logits, ld, nv, tok, step, lp_out, lp_hist,
+                           hist_stride, 1);
 }
 
 // ------------------------------------------------------- top-K alternatives

@@ -65,6 +65,7 @@ static const std::vector<FuseOption> &fuse_options() {
         {"top_k", "QASR_TOP_K", &FuseCfg::top_k},
         {"lmh_topk", "QASR_LMH_TOPK", &FuseCfg::lmh_topk},
         {"beam_width", "QASR_BEAM_WIDTH", &FuseCfg::beam_width},
+        {"sample_slices", "QASR_SAMPLE_SLICES", &FuseCfg::sample_slices},
     };
     return v;
 }
@@ -365,6 +366,7 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
             if (n == "poll_limit" && value <= 0) return fail(QASR_ERR_ARG, "poll_limit must be positive");
             if (n == "top_k" && (value < 0 || value > QASR_TOPK_MAX)) return fail(QASR_ERR_ARG, "top_k out of range (0..8)");
             if (n == "beam_width" && (value < 0 || value > QASR_BEAM_MAX)) return fail(QASR_ERR_ARG, "beam_width out of range (0..8)");
+            if (n == "sample_slices" && value < 0) return fail(QASR_ERR_ARG, "sample_slices must be >= 0");
             if (n == "beam_width" && value >= 2) {
                 HIPCHK(hipSetDevice(c->m->device));
                 if (const int rc = ensure_beam(c)) return rc;
@@ -409,6 +411,7 @@ extern "C" int qasr_ctx_get_option(const qasr_ctx *c, const char *name, int *val
     if (n == "fused_mode") { *value = c->last_fmode; return 0; }
     if (n == "fused_exact") { *value = c->last_fx; return 0; }
     if (n == "attn_path") { *value = c->last_attn; return 0; }
+    if (n == "graph_captures") { *value = (int)c->n_captures; return 0; }
     if (n == "slots_qkv") { *value = std::min(c->fuse.slots_qkv64, c->fuse.slots_qkv128); return 0; }
     for (const auto &o : fuse_options())
         if (n == o.name) { *value = c->fuse.*(o.field); return 0; }

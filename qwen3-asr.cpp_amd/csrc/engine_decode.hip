@@ -63,6 +63,10 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     const bool tk = K > 0;
     const bool tk_fused = tk && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && K <= kLmhTopkAutoMax));
     if (tk && !tk_fused) want_logits = true;
+    // sampling: the draw reads the fp32 logits after the bookkeeping, and the drawn token's log-probability comes from
+    // them too (the fused LSE's value would be the argmax's)
+    const bool smp = sampling_on(c);
+    if (smp) want_logits = true;
     int rc;
     const size_t layer_kv = (size_t)c->max_batch * hp.n_kv_head * c->max_ctx * 128;
     const int nl = step_layers(c);   // diagnostic layer cap
@@ -231,12 +235,12 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
             lm.stamp = stamp;
             if (skinny) {   // amax / done are zero at rest: the LM head's last workgroup re-arms them
                 launch_gemv(EPI_ARGMAX, lm, s);
-                if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+                if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
                 if (tk && (rc = topk_step(c, B))) return rc;
             } else {   // norm + GEMM + argmax + bookkeeping in one launch (lmhead.hip)
                 lm.nkv = c->d_nkv;
                 // (the top-K variant carries the log-sum-exp code: d_lp / d_lphist are written with either option)
-                if (lp || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
+                if ((lp && !smp) || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
                 if (tk_fused) {
                     lm.tk_part = c->d_tkpart; lm.tk_out = c->d_tkid; lm.tk_lp = c->d_tklp; lm.tk_hist = c->d_tkhid;
                     lm.tk_lphist = c->d_tkhlp; lm.tk_k = K;
@@ -257,10 +261,12 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     if (r.in(2 + 2 * nl) && !skinny && !lmh_one) {   // bookkeeping (fused into the LM-head GEMV at batch <= 8)
         launch_step_advance(c->d_pos, c->d_nkv, c->d_step, B, s);
         launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
-        if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+        if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
         if (tk && (rc = topk_step(c, B))) return rc;
         launch_fill_u64(c->d_amax, B, 0ull, s);   // re-arm (zero at rest)
     }
+    // sampling: the draw replaces the greedy choice in d_tok and in the history slot the bookkeeping just wrote
+    if (smp && r.in(skinny || lmh_one ? 1 + 2 * nl : 2 + 2 * nl) && (rc = sample_step(c, B, 1))) return rc;
     // a beam run: the beam step replaces the greedy choice in d_tok, then the fork (the grid covers the bucket's keys)
     if (c->beam_W >= 2 && r.in(skinny || lmh_one ? 1 + 2 * nl : 2 + 2 * nl) &&
         (rc = beam_step(c, B / c->beam_W, (std::min(c->max_ctx, splits * decode_split_len()) + 7) / 8)))
@@ -321,6 +327,7 @@ static int capture(qasr_ctx *c, int B, bool want_logits, StepRange r, int splits
     }
     HIPCHK(hipGraphInstantiate(out, gr, nullptr, nullptr, 0));
     HIPCHK(hipGraphDestroy(gr));
+    c->n_captures++;
     return 0;
 }
 
@@ -345,7 +352,7 @@ int qasr::eng::decode_graph(qasr_ctx *c, int B, bool want_logits, int base) {
 
 static int step_graphs(qasr_ctx *c, int splits, qasr_ctx::StepGraphs **out) {
     const int B = c->graph_B;
-    auto &gs = c->graphs[std::make_tuple(c->beam_W, B, splits)];   // (a beam run's steps are graphs of their own)
+    auto &gs = c->graphs[std::make_tuple(step_mode(c), B, splits)];   // (a beam run's and a sampling run's steps are graphs of their own)
     int rc;
     if (!gs.full && (rc = capture(c, B, c->graph_logits, kWholeStep, splits, &gs.full))) return rc;
     if (c->probe && !gs.pre) {

@@ -7,6 +7,7 @@
 //   engine_decode.hip  the decode-step emitter, graph capture, kernel probes, qasr_decode_step
 //   engine_run.hip     qasr_run, the continuous-batching stream, their log-probability readers
 //   engine_beam.hip    beam search: the KV-cache fork entry, the beam loop, the hypothesis reader
+//   engine_sample.hip  temperature sampling: qasr_set_sampling, the sampler step, the n_best run, the sample reader
 //   engine_score.hip   teacher-forced scoring: the score head over prefill rows, qasr_prefill_score, qasr_score
 //   engine_align.hip   the forced aligner and its JSON output
 #pragma once
@@ -190,6 +191,22 @@ struct qasr_ctx {
                                        // the fork, and its top-K runs with K = W); else 0
     bool last_run_beam = false;        // the last qasr_run was a beam run (qasr_get_logprobs / qasr_get_topk refuse)
     std::vector<std::vector<qasr::BeamHyp>> beam_res;   // its hypotheses per clip, best first
+    // temperature sampling (engine_sample.hip): off while samp.temperature <= 0.  The device state is
+    // allocated the first time it is turned on (ensure_sample): the scalars a captured step reads, per row the draw's
+    // identity (clip, sample, t) and the key the slices fold into (zero at rest)
+    qasr_sampling samp = {0.f, 0.f, 0, 1};
+    struct SampleDev {
+        qasr::SampleScalars *sc = nullptr;
+        int *clip = nullptr, *sample = nullptr, *t = nullptr;
+        unsigned long long *skey = nullptr;
+    } sd;
+    int samp_run_N = 0;                // inside a sampling qasr_run: its n_best (the prefill then draws n_best rows a clip); else 0
+    std::vector<int> run_clip_ids;     // qasr_run_staged: the pool indices of the subset (the draws' clip identities)
+    bool last_run_sampled = false;     // the last qasr_run drew its tokens (qasr_get_samples reads samp_res)
+    int last_run_nbest = 0;            // ... with this n_best
+    struct SampleHyp { std::vector<int32_t> tokens; std::vector<float> logprobs; float sum = 0.f; };
+    std::vector<std::vector<SampleHyp>> samp_res;   // its hypotheses per clip, in sample order
+    long n_captures = 0;               // step graphs captured so far (option "graph_captures", read-only)
     DevBuf fork_args;                  // qasr_kv_fork: the caller's parent | from | to on the device
     // teacher-forced scoring (engine_score.hip): the gathered normed rows (fp16), row indices | targets, the three
     // outputs of a block of rows, the score head's scratch
@@ -243,7 +260,7 @@ struct qasr_ctx {
     // decode graphs, one set per attention split-grid bucket (the grid must
     // cover the longest sequence's context: it grows by 64 keys per split)
     struct StepGraphs { hipGraphExec_t full = nullptr, pre = nullptr, post = nullptr; };
-    std::map<std::tuple<int, int, int>, StepGraphs> graphs;   // key: (beam_W, batch, split bucket)
+    std::map<std::tuple<int, int, int>, StepGraphs> graphs;   // key: (step_mode: beam_W, sampling and n_best; batch; split bucket)
     int graph_B = -1;
     bool graph_logits = false;
     int graph_base = 0;            // max prompt length of the current run: step k feeds position base + k
@@ -288,6 +305,11 @@ int topk_step(qasr_ctx *c, int B);
 inline int step_k(const qasr_ctx *c) { return c->beam_W >= 2 ? c->beam_W : c->fuse.top_k; }
 int ensure_topk(qasr_ctx *c);
 int ensure_beam(qasr_ctx *c);
+// sampling: on for this context's decoding (aligner models ignore it); the rows a prefill draws per sequence; the
+// graph key's first entry (a beam run's width, or 16 x the rows per clip of a sampling step)
+inline bool sampling_on(const qasr_ctx *c) { return c->samp.temperature > 0.f && !c->m->hp.aligner; }
+inline int sample_mul(const qasr_ctx *c) { return std::max(1, c->samp_run_N); }
+inline int step_mode(const qasr_ctx *c) { return c->beam_W >= 2 ? c->beam_W : sampling_on(c) ? 16 * sample_mul(c) : 0; }
 int dev_alloc(qasr_ctx *c, void **p, size_t bytes);
 
 // V^T cache elements of one layer
@@ -350,6 +372,20 @@ KvForkArgs fork_args(qasr_ctx *c, const int *parent, const int *from, const int 
 int beam_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
 // the beam step and the fork that end a decode step of a beam run (blocks: 8-key blocks the fork's grid covers)
 int beam_step(qasr_ctx *c, int G, int blocks);
+
+// engine_sample.hip
+// the draw that ends a sampling prefill or decode step: B rows, row r from logits row r / src_div; then the drawn
+// tokens' log-probabilities at T = 1 into d_lp / d_lphist
+int sample_step(qasr_ctx *c, int B, int src_div);
+int sample_set_streams(qasr_ctx *c, const std::vector<int> &clip, const std::vector<int> &sample, const std::vector<int> &t);
+int sample_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
+// the hypotheses of a sampling run from its token history (rows g * N + i) and d_lphist -> c->samp_res
+int sample_collect(qasr_ctx *c, int G, int N, const std::vector<int32_t> &hist, int steps, int max_tokens, int ignore_eos);
+
+// engine_run.hip
+int greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::vector<int32_t> &hist, int &steps);
+int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const std::vector<int32_t> &hist, int steps, int32_t *tokens,
+                int *n_tokens, qasr_timings *t);
 
 // engine_decode.hip
 int split_bucket(qasr_ctx *c, int pos);

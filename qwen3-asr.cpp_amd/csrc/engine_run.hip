@@ -64,7 +64,7 @@ static int front_end(qasr_ctx *c, const float *d_pcm, const std::vector<long> &o
 // ---------------------------------------------------------------- qasr_run
 // greedy loop (src/qwen3_asr.cpp:270-296): step k feeds token k at position P+k-1.
 // Leaves the device token history in hist ([B][hist_cap]) and the steps run in steps.
-static int greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::vector<int32_t> &hist, int &steps) {
+int qasr::eng::greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::vector<int32_t> &hist, int &steps) {
     const Hparams &hp = c->m->hp;
     hipStream_t s = c->st;
     int rc;
@@ -157,8 +157,8 @@ int qasr::eng::run_timings(qasr_ctx *c, int steps, qasr_timings *t) {
 // after the timed span of a run: the device error word, probe and profile
 // records, then the history's rows as the caller's tokens (and their
 // log-probabilities, option token_logprobs) and the stage timings
-static int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const std::vector<int32_t> &hist, int steps,
-                       int32_t *tokens, int *n_tokens, qasr_timings *t) {
+int qasr::eng::run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const std::vector<int32_t> &hist, int steps,
+                           int32_t *tokens, int *n_tokens, qasr_timings *t) {
     const Hparams &hp = c->m->hp;
     hipStream_t s = c->st;
     int rc;
@@ -259,6 +259,8 @@ extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *to
     if (!c || max_tokens <= 0 || !tokens || !n_tokens) return fail(QASR_ERR_ARG, "bad arguments");
     const int B = (int)c->staged_n.size();
     if (B == 0) return fail(QASR_ERR_STATE, "no staged audio");
+    if (sampling_on(c)) return sample_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
+    c->last_run_sampled = false;
     if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return beam_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
     c->last_run_beam = false;
     if (B > c->max_batch) return fail(QASR_ERR_ARG, "staged clips exceed the context's max_batch (qasr_run_staged runs subsets)");
@@ -301,7 +303,9 @@ extern "C" int qasr_run_staged(qasr_ctx *c, const int *clips, int B, int max_tok
     }
     std::swap(n, c->staged_n);
     std::swap(off, c->staged_off);
+    c->run_clip_ids.assign(clips, clips + B);   // (a sampling run keys its draws by the pool index)
     const int rc = qasr_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
+    c->run_clip_ids.clear();
     std::swap(n, c->staged_n);   // the staged pool stays for the next subset
     std::swap(off, c->staged_off);
     return rc;
@@ -339,6 +343,7 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                       int max_tokens, int ignore_eos, qasr_stream_stats *stats) {
     if (!c || !sink || max_tokens <= 0 || slots < 0 || slots > c->max_batch) return fail(QASR_ERR_ARG, "bad arguments");
     if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return fail(QASR_ERR_STATE, "the continuous-batching stream has no beam search (option beam_width >= 2)");
+    if (sampling_on(c)) return fail(QASR_ERR_STATE, "the continuous-batching stream has no sampling (qasr_set_sampling)");
     HIPCHK(hipSetDevice(c->m->device));
     const int S = slots ? slots : c->max_batch;
     std::unique_lock<std::mutex> dev_lk;
@@ -588,6 +593,7 @@ extern "C" int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens)
     if (!c || !out || B <= 0 || max_tokens <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     if (!c->fuse.token_logprobs) return fail(QASR_ERR_STATE, "option token_logprobs is off");
     if (c->last_run_beam) return fail(QASR_ERR_STATE, "the last run was a beam run: its values are qasr_get_beams'");
+    if (c->last_run_sampled && c->last_run_nbest >= 2) return fail(QASR_ERR_STATE, "the last run drew n_best >= 2 samples: their values are qasr_get_samples'");
     if (!c->lp_run_B) return fail(QASR_ERR_STATE, "no run has finished with option token_logprobs on");
     if (B < c->lp_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
     for (int b = 0; b < c->lp_run_B; b++)
@@ -613,6 +619,7 @@ extern "C" int qasr_get_topk(qasr_ctx *c, int32_t *ids, float *logprobs, int B, 
     if (!c->fuse.top_k) return fail(QASR_ERR_STATE, "option top_k is off");
     if (K != c->fuse.top_k) return fail(QASR_ERR_ARG, "K differs from option top_k");
     if (c->last_run_beam) return fail(QASR_ERR_STATE, "the last run was a beam run: its values are qasr_get_beams'");
+    if (c->last_run_sampled && c->last_run_nbest >= 2) return fail(QASR_ERR_STATE, "the last run drew n_best >= 2 samples: qasr_get_samples reads them");
     if (!c->tk_run_B) return fail(QASR_ERR_STATE, "no run has finished with option top_k on");
     if (B < c->tk_run_B) return fail(QASR_ERR_ARG, "buffer holds fewer rows than the last run's batch");
     for (int b = 0; b < c->tk_run_B; b++)

@@ -403,7 +403,8 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     launch_rmsnorm_f16(x, H, c->plast.as<int>(), B, H, m->out_norm, hp.rms_eps, xl, s);
     launch_fill_u64(c->d_amax, B, 0ull, s);
     const bool lp = c->fuse.token_logprobs != 0;   // the log-probabilities come from the fp32 logits
-    want_logits = want_logits || lp || step_k(c) > 0;   // (option top_k or a beam run: the alternatives likewise)
+    const bool smp = sampling_on(c);   // sampling: the draw and its log-probability read them too
+    want_logits = want_logits || lp || step_k(c) > 0 || smp;   // (option top_k or a beam run: the alternatives likewise)
     if (B <= 8) {
         GemvArgs gv{};
         gv.xh = xl; gv.ldxh = H; gv.W = m->embd; gv.K = H; gv.N = hp.vocab; gv.M = B;
@@ -417,9 +418,11 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     }
     HIPCHK(hipMemsetAsync(c->d_step, 0, 4, s));
     launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
-    if (lp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+    if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
     if ((rc = topk_step(c, B))) return rc;
     launch_fill_u64(c->d_amax, B, 0ull, s);   // zero at rest for the decode graph
+    // sampling: token t = 0 of every hypothesis from the prefill's logits (an n_best run: n_best rows a clip from its one row)
+    if (smp && (rc = sample_step(c, B * sample_mul(c), sample_mul(c)))) return rc;
     // decode state: next position = P_b, n_kv = P_b + 1 (the fed token's own key included)
     std::vector<int> pos(B), nkv(B);
     for (int b = 0; b < B; b++) {

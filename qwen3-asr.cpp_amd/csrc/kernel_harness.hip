@@ -359,3 +359,58 @@ extern "C" int qasr_kt_score_head(int device, qasr_kt_score_args *a) {
     if ((rc = get(lp, a->lp)) || (rc = get(gid, a->gid)) || (rc = get(glp, a->glp))) return rc;
     return 0;
 }
+
+// ------------------------------------------------------------------ sampling
+extern "C" int qasr_kt_sample(int device, qasr_kt_sample_args *a) {
+    if (!a) return fail(QASR_ERR_ARG, "bad arguments");
+    int rc;
+    if (a->dump_n > 0) {   // G(u_n) over a range of n
+        if (!a->dump || (uint64_t)a->dump_n0 + a->dump_n > (1ull << 23)) return fail(QASR_ERR_ARG, "dump range outside [0, 2^23)");
+        if ((rc = use_device(device))) return rc;
+        KtBuf d;
+        d.bytes = (size_t)a->dump_n * 4;
+        HIPCHK(hipMalloc((void **)&d.d, d.bytes));
+        HIPCHK(hipMemset(d.d, 0xFF, d.bytes));
+        launch_sample_gumbel_dump(a->dump_n0, a->dump_n, d.ptr<float>(), nullptr);
+        if ((rc = finish_plain(&a->declined, true))) return rc;
+        return get(d, a->dump);
+    }
+    if (a->R <= 0 || a->ld <= 0 || a->n_valid <= 0 || a->n_valid > a->ld || a->src_div < 1 || a->R % a->src_div != 0 || a->slices < 0 ||
+        a->guard < 0 || a->launches < 1 || !a->logits || !a->greedy || !a->clip || !a->sample || !a->t || !a->tok || !a->key || !a->hist ||
+        !a->t_out || !a->skey_out)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const int R = a->R, RS = R / a->src_div, G = a->guard;
+    for (int r = 0; r < RS; r++)
+        if (a->greedy[r] < 0 || a->greedy[r] >= a->n_valid) return fail(QASR_ERR_ARG, "greedy id outside [0, n_valid)");
+    if ((rc = use_device(device))) return rc;
+    KtBuf lg, gr, cl, sm, t, sc, step, tok, key, hist;
+    KtFenced skey;
+    const SampleScalars scal{a->inv_T, a->cut, (uint32_t)(a->seed & 0xffffffffull), (uint32_t)(a->seed >> 32)};
+    const int zero = 0;
+    std::vector<unsigned long long> rest(R, 0ull);
+    if ((rc = put_in(lg, a->logits, RS, a->ld, 4, G, 0xFF)) || (rc = put_state(gr, a->greedy, (size_t)RS * 4)) ||
+        (rc = put_state(cl, a->clip, (size_t)R * 4)) || (rc = put_state(sm, a->sample, (size_t)R * 4)) ||
+        (rc = put_state(t, a->t, (size_t)R * 4)) || (rc = put_state(sc, &scal, sizeof scal)) || (rc = put_state(step, &zero, 4)) ||
+        (rc = put_out(tok, a->tok, R, 1, 4, G)) || (rc = put_out(key, a->key, R, 1, 4, G)) || (rc = put_out(hist, a->hist, R, 1, 4, G)) ||
+        (rc = skey.put(rest.data(), (size_t)R * 8)))
+        return rc;
+    SampleArgs s{};
+    s.logits = lg.ptr<float>(); s.ld = a->ld; s.n_valid = a->n_valid;
+    s.greedy = gr.ptr<int32_t>();
+    s.clip = cl.ptr<int>(); s.sample = sm.ptr<int>(); s.t = t.ptr<int>();
+    s.sc = sc.ptr<SampleScalars>(); s.skey = skey.b.ptr<unsigned long long>();
+    s.tok = tok.ptr<int32_t>(); s.hist = hist.ptr<int32_t>(); s.hist_stride = 1; s.step = step.ptr<int>();
+    s.key_out = key.ptr<float>();
+    s.R = R; s.src_div = a->src_div;
+    bool ran = true;
+    for (int i = 0; i < a->launches && ran; i++) {
+        if (i) HIPCHK(hipMemcpy(t.d, a->t, (size_t)R * 4, hipMemcpyHostToDevice));   // (the same draw again)
+        ran = launch_sample(s, a->slices, nullptr);
+        if (ran && i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
+    }
+    if ((rc = finish(a, ran))) return rc;
+    if ((rc = get(tok, a->tok)) || (rc = get(key, a->key)) || (rc = get(hist, a->hist)) || (rc = get(t, a->t_out)) ||
+        (rc = skey.take(a->skey_out, "the key scratch")))
+        return rc;
+    return 0;
+}

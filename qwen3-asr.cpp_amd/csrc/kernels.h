@@ -251,6 +251,7 @@ struct FuseCfg {
                                         // utterance sets over a smaller pool); 0: such an id is rejected as out of range
     int poison = 0;                     // test only: scratch buffers grown by the context are filled with 0xFF bytes
                                         // (fp16 NaN) so a kernel reading rows it never wrote shows up in its outputs
+    int sample_slices = 0;              // sampling: workgroups a row's key kernel is spread over (0: sample_slices(), sample.hip)
     int token_logprobs = 0;             // every greedy step also yields the log-probability of its argmax token
                                         // (qasr_get_*logprobs): in the one-launch LM head where that runs (lmhead.hip
                                         // LSE), else from the fp32 logits by launch_token_logprob; 0: nothing changes
@@ -441,8 +442,9 @@ void launch_fill_u64(unsigned long long *p, int n, unsigned long long v, hipStre
 // head wrote: lp = logits[b][tok[b]] - logsumexp(logits[b][0 .. n_valid)), to
 // lp_out[b] and lp_hist[b][*step] (the slot of the token just written to hist);
 // n_valid = 0: every column
+// src_div > 1: row b reads logits row b / src_div (the first step of an n_best run: one prefill row a clip)
 void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const int32_t *tok, const int *step, float *lp_out,
-                          float *lp_hist, int hist_stride, hipStream_t s);
+                          float *lp_hist, int hist_stride, hipStream_t s, int src_div = 1);
 // the K (1 .. TOPK_MAX) largest logits of each row of the fp32 logits [B][ld], descending, equal values by
 // lower column first (entry 0 is the greedy token), as ids and log-probabilities
 // logit - logsumexp(logits[b][0 .. n_valid)): to tk_ids / tk_lp [B][K] and, where the histories are
@@ -490,5 +492,33 @@ struct BeamSelectArgs {
     const int32_t *eos;                  // [1]
 };
 bool launch_beam_select(const BeamSelectArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------- sampling (sample.hip)
+// A seeded Gumbel-max draw per row from fp32 logits (the normative rule): row r draws from logits
+// row r / src_div (src_div = n_best at a hypothesis' first step, where the prefill wrote one row a clip; else 1)
+// among the columns j with l[j] >= l[greedy] + cut, the key fmaf(l[j], inv_T, G(u)) with u from
+// Philox4x32-10(counter {j >> 2, t, clip, sample}, key seed)[j & 3]; largest key, equal keys by lower column.
+// The scalars and the per-row identities are device memory, so a captured step serves any of their values.
+struct SampleScalars {
+    float inv_T, cut;                    // 1 / T and T * logf(min_p) (-inf: no cut), both rounded on the host
+    uint32_t seed_lo, seed_hi;
+};
+struct SampleArgs {
+    const float *logits; int ld, n_valid;   // [R / src_div][ld]
+    const int32_t *greedy;               // [R / src_div] each logits row's argmax (d_tok before the draw)
+    const int *clip, *sample;            // [R] the draw's identity ...
+    int *t;                              // [R] ... and its token index, advanced by the launch
+    const SampleScalars *sc;             // [1]
+    unsigned long long *skey;            // [R] zero at rest, re-armed by the launch
+    int32_t *tok;                        // [R] out: the drawn tokens (may alias greedy)
+    int32_t *hist; int hist_stride; const int *step;   // hist[r][*step] = tok[r] (hist null: not written)
+    float *key_out;                      // [R] the winning keys (null: not written)
+    int R, src_div;
+};
+// slices a row is spread over where the caller passes 0
+int sample_slices(int R, int n_valid);
+bool launch_sample(const SampleArgs &a, int slices, hipStream_t s);   // false = bad shape, nothing launched
+// test only: out[i] = G(u_n) of the rule's step 2 and 3 for n = n0 + i
+void launch_sample_gumbel_dump(uint32_t n0, uint32_t n, float *out, hipStream_t s);
 
 }  // namespace qasr

@@ -36,6 +36,9 @@ struct cli_params {
     int32_t top_k = 0;       // --top-k: alternatives per token (transcribe_params::top_k)
     int32_t beam_width = 0;  // --beam-width: beam search of this width (transcribe_params::beam_width)
     bool beams = false;      // --beams: list every hypothesis of a beam run
+    float temperature = 0.f, min_p = 0.f;   // --temperature / --min-p / --seed / --n-best: sampling (transcribe_params)
+    uint64_t seed = 0;
+    int32_t n_best = 1;
     std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
 };
@@ -55,6 +58,11 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
     fprintf(stderr, "  --beam-width <n>       Beam search of width n (2..8) instead of greedy decoding\n");
     fprintf(stderr, "  --beams                With --beam-width: list every hypothesis with its summed log-probability\n");
+    fprintf(stderr, "  --temperature <T>      Sample every token from softmax(logits / T), 0 < T <= 100, instead of greedy decoding\n");
+    fprintf(stderr, "  --min-p <p>            With --temperature: only tokens at least p (0..1) times as probable as the greedy one\n");
+    fprintf(stderr, "  --seed <n>             With --temperature: the 64-bit seed of the draws (default: 0)\n");
+    fprintf(stderr, "  --n-best <n>           With --temperature: n (1..8) samples a file; n > 1 lists every sample with its\n");
+    fprintf(stderr, "                         summed log-probability (the output is sample 0's text)\n");
     fprintf(stderr, "  --score <text>         Score <text> as a transcript of the -f file instead of transcribing (repeatable):\n");
     fprintf(stderr, "                         per text the summed log-probability, the mean per token and the token count\n");
     fprintf(stderr, "                         (the EOS included); with --tokens every token's id, text and log-probability,\n");
@@ -127,6 +135,22 @@ static bool parse(int argc, char **argv, cli_params &p) {
             if (p.beam_width < 2 || p.beam_width > 8) { fprintf(stderr, "Error: --beam-width takes 2..8\n"); return false; }
         }
         else if (!strcmp(a, "--beams")) p.beams = true;
+        else if (!strcmp(a, "--temperature")) {
+            if (!val(v)) return false;
+            p.temperature = (float)atof(v.c_str());
+            if (!(p.temperature > 0.f && p.temperature <= 100.f)) { fprintf(stderr, "Error: --temperature takes 0 < T <= 100\n"); return false; }
+        }
+        else if (!strcmp(a, "--min-p")) {
+            if (!val(v)) return false;
+            p.min_p = (float)atof(v.c_str());
+            if (!(p.min_p >= 0.f && p.min_p <= 1.f)) { fprintf(stderr, "Error: --min-p takes 0..1\n"); return false; }
+        }
+        else if (!strcmp(a, "--seed")) { if (!val(v)) return false; p.seed = strtoull(v.c_str(), nullptr, 0); }
+        else if (!strcmp(a, "--n-best")) {
+            if (!val(v)) return false;
+            p.n_best = atoi(v.c_str());
+            if (p.n_best < 1 || p.n_best > 8) { fprintf(stderr, "Error: --n-best takes 1..8\n"); return false; }
+        }
         else if (!strcmp(a, "--score")) { if (!val(v)) return false; p.score_texts.push_back(v); }
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
@@ -434,6 +458,10 @@ static int run_transcription(const cli_params &p) {
     tp.token_logprobs = p.logprobs;
     tp.top_k = p.top_k;
     tp.beam_width = p.beam_width;
+    tp.temperature = p.temperature;
+    tp.min_p = p.min_p;
+    tp.seed = p.seed;
+    tp.n_best = p.n_best;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));
@@ -472,6 +500,13 @@ static int run_transcription(const cli_params &p) {
                 const auto &h = r.beams[i];
                 fprintf(stderr, "  [%zu] %.4f  %zu tokens%s  \"%s\"\n", i, h.sum_logprob, h.tokens.size(), h.finished ? "" : " (unfinished)",
                         h.text.c_str());
+            }
+        }
+        if (r.samples.size() > 1) {   // --n-best > 1: every sample, in the layout of --beams
+            fprintf(stderr, "%s: %zu samples\n", p.audio_paths[f].c_str(), r.samples.size());
+            for (size_t i = 0; i < r.samples.size(); ++i) {
+                const auto &h = r.samples[i];
+                fprintf(stderr, "  [%zu] %.4f  %zu tokens  \"%s\"\n", i, h.sum_logprob, h.tokens.size(), h.text.c_str());
             }
         }
         if (lp && !r.tokens.empty()) {

@@ -133,6 +133,16 @@ bool Qwen3ASR::set_beam_width(int w) {
     return true;
 }
 
+// sampling as the call asks (qasr_set_sampling: no graph is dropped either way)
+bool Qwen3ASR::set_sampling(const transcribe_params &params) {
+    qasr_sampling sp{params.temperature, params.min_p, params.seed, params.n_best};
+    if (qasr_set_sampling(ctx_, params.temperature > 0.f ? &sp : nullptr) != 0) {
+        error_msg_ = std::string("Failed to set sampling: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
 transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const transcribe_params &params) {
     transcribe_result result;
     if (!model_) { result.error_msg = "Model not loaded"; return result; }
@@ -180,8 +190,12 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     // beam search: W decode rows a clip, no per-token progress, its values through qasr_get_beams
     const int W = params.beam_width >= 2 ? params.beam_width : 1;
     const bool beam = W >= 2;
-    if (!ensure_ctx(B * W, maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
-        !set_top_k(params.top_k) || !set_beam_width(params.beam_width)) {
+    // sampling: n_best decode rows a clip; n_best >= 2 delivers its values through qasr_get_samples alone
+    const bool sampling = params.temperature > 0.f;
+    const int NB = sampling ? std::max(params.n_best, 1) : 1;
+    const bool many = sampling && NB >= 2;
+    if (!ensure_ctx(B * std::max(W, NB), maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
+        !set_top_k(params.top_k) || !set_beam_width(params.beam_width) || !set_sampling(params)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -191,7 +205,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     std::vector<int> nt(B);
     qasr_timings tm{};
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
-    const bool per_token = !beam && (progress_callback_ || params.print_progress);
+    const bool per_token = !beam && !many && (progress_callback_ || params.print_progress);
     qasr_set_token_callback(ctx_, per_token ? token_cb : nullptr, per_token ? &tcb : nullptr);
     const int rc = qasr_transcribe_batch(ctx_, ptr.data(), n.data(), B, params.max_tokens, 0, toks.data(), nt.data(), &tm);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
@@ -206,7 +220,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         rep.resize(std::max(len, 0));
         profile_report_ = rep;
     }
-    const bool want_lp = params.token_logprobs && !beam;
+    const bool want_lp = params.token_logprobs && !beam && !many;
     std::vector<float> lps;
     if (want_lp) {
         lps.resize((size_t)B * params.max_tokens);
@@ -215,7 +229,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
             return out;
         }
     }
-    const int K = beam ? 0 : params.top_k;
+    const int K = beam || many ? 0 : params.top_k;
     std::vector<int32_t> alt_id;
     std::vector<float> alt_lp;
     if (K > 0) {
@@ -263,6 +277,24 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
                 r.beams.push_back(std::move(h));
             }
         }
+        if (sampling) {
+            std::vector<int32_t> st((size_t)NB * params.max_tokens);
+            std::vector<float> sl(st.size()), ss(NB);
+            std::vector<int> sn(NB);
+            const int nh = qasr_get_samples(ctx_, b, st.data(), sl.data(), sn.data(), ss.data(), NB, params.max_tokens);
+            if (nh < 0) {
+                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+                continue;
+            }
+            for (int i = 0; i < nh; i++) {
+                sample_hypothesis h;
+                h.tokens.assign(st.begin() + (long)i * params.max_tokens, st.begin() + (long)i * params.max_tokens + sn[i]);
+                h.token_logprobs.assign(sl.begin() + (long)i * params.max_tokens, sl.begin() + (long)i * params.max_tokens + sn[i]);
+                h.text = detok(h.tokens);
+                h.sum_logprob = ss[i];
+                r.samples.push_back(std::move(h));
+            }
+        }
         r.success = true;
         r.t_mel_ms = (int64_t)tm.t_mel_ms;
         r.t_encode_ms = (int64_t)tm.t_encode_ms;
@@ -278,9 +310,9 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
 std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std::vector<float>> &clips,
                                                           const transcribe_params &params) {
     if (clips.size() <= 1) return transcribe_run(clips, params);
-    if (params.beam_width >= 2) {   // the stream has no beam search: whole runs of as many clips as max_batch() rows hold
+    if (params.beam_width >= 2 || params.temperature > 0.f) {   // the stream has neither beam search nor sampling: whole runs of as many clips as max_batch() rows hold
         std::vector<transcribe_result> out;
-        const size_t per = (size_t)std::max(1, max_batch_ / params.beam_width);
+        const size_t per = (size_t)std::max(1, max_batch_ / std::max(1, params.beam_width >= 2 ? params.beam_width : params.n_best));
         for (size_t i = 0; i < clips.size(); i += per) {
             std::vector<std::vector<float>> part(clips.begin() + i, clips.begin() + std::min(clips.size(), i + per));
             for (auto &r : transcribe_run(part, params)) out.push_back(std::move(r));
@@ -373,7 +405,10 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     const int need = n_ctx > 0 ? n_ctx : qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(30 * 16000))) + (int)sys.size() + params.max_tokens;
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
     if (params.beam_width >= 2) { error_msg_ = "The stream has no beam search (transcribe_params::beam_width)"; return false; }
-    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) || !set_beam_width(0)) return false;
+    if (params.temperature > 0.f) { error_msg_ = "The stream has no sampling (transcribe_params::temperature)"; return false; }
+    if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) || !set_beam_width(0) ||
+        !set_sampling(params))
+        return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};

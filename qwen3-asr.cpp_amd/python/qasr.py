@@ -38,6 +38,7 @@ EXPORTS = [
     "qasr_get_step_topk", "qasr_get_topk", "qasr_stream_topk",
     "qasr_kv_fork", "qasr_get_beams", "qasr_prefill_slots",
     "qasr_prefill_score", "qasr_score",
+    "qasr_set_sampling", "qasr_get_sampling", "qasr_set_sample_streams", "qasr_get_samples",
 ]
 
 
@@ -62,7 +63,13 @@ class StreamStats(C.Structure):
                 ("t_encode_ms", C.c_double), ("kv_keys", C.c_int64)]
 
 
+class Sampling(C.Structure):
+    """qasr_sampling"""
+    _fields_ = [("temperature", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64), ("n_best", C.c_int32)]
+
+
 QASR_BEAM_MAX = 8
+QASR_SAMPLE_MAX = 8
 _lib = None
 # void (*)(void *user, int seq, int n_generated, int32_t token)
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int32)
@@ -125,6 +132,9 @@ def lib() -> C.CDLL:
             "qasr_prefill_slots": ([P, I32P, IP, F, IP, IP, IP, I, F, I32P], I),
             "qasr_prefill_score": ([P, I32P, IP, IP, F, IP, IP, IP, I, I32P, F, I32P, F, I], I),
             "qasr_score": ([P, IP, I32P, IP, I, I, F, I32P, F, F, C.POINTER(Timings)], I),
+            "qasr_set_sampling": ([P, C.POINTER(Sampling)], I), "qasr_get_sampling": ([P, C.POINTER(Sampling)], I),
+            "qasr_set_sample_streams": ([P, I32P, I32P, I32P, I], I),
+            "qasr_get_samples": ([P, I, I32P, F, IP, F, I, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -308,6 +318,16 @@ class RunResult:
     # every hypothesis of every clip of a beam run (context option "beam_width" >= 2), best first; tokens[b] is
     # beams[b][0].tokens; None after a greedy run
     beams: Optional[List[List["Beam"]]] = None
+    # every hypothesis of every clip of a sampling run (Context.set_sampling), in sample order; tokens[b] is
+    # samples[b][0].tokens; None with sampling off
+    samples: Optional[List[List["Sample"]]] = None
+
+
+@dataclass
+class Sample:
+    tokens: List[int]
+    logprobs: List[float]      # log softmax(logits)[token] at T = 1, one per token (a popped EOS takes its value with it)
+    sum_logprob: float         # ... but the sum counts the EOS step
 
 
 @dataclass
@@ -530,6 +550,45 @@ class Context:
             raise QasrError(f"qasr_get_beams: {lib().qasr_last_error().decode(errors='replace')}")
         return [Beam(toks[i, :nt[i]].tolist(), lps[i, :nt[i]].tolist(), float(sums[i]), bool(fin[i])) for i in range(n)]
 
+    def set_sampling(self, temperature: float = 0.0, min_p: float = 0.0, seed: int = 0, n_best: int = 1) -> None:
+        """qasr_set_sampling: temperature <= 0 turns sampling off"""
+        sp = Sampling(float(temperature), float(min_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_best))
+        _check(lib().qasr_set_sampling(self.h, C.byref(sp)), "qasr_set_sampling")
+
+    def get_sampling(self) -> Sampling:
+        sp = Sampling()
+        _check(lib().qasr_get_sampling(self.h, C.byref(sp)), "qasr_get_sampling")
+        return sp
+
+    def set_sample_streams(self, clip, sample, t) -> None:
+        """qasr_set_sample_streams: the (clip, sample, t) identities rows 0 .. B - 1 of prefill / decode_step draw with"""
+        cl, sm, tt = (np.ascontiguousarray(x, np.int32) for x in (clip, sample, t))
+        _check(lib().qasr_set_sample_streams(self.h, _i32(cl), _i32(sm), _i32(tt), len(cl)), "qasr_set_sample_streams")
+
+    def samples(self, clip: int) -> List[Sample]:
+        """qasr_get_samples: the hypotheses of clip `clip` of the last sampling run, in sample order"""
+        W, T = QASR_SAMPLE_MAX, self.max_ctx
+        toks, lps = np.zeros((W, T), np.int32), np.zeros((W, T), np.float32)
+        nt, sums = np.zeros(W, np.int32), np.zeros(W, np.float32)
+        n = lib().qasr_get_samples(self.h, int(clip), _i32(toks), _f(lps), _i(nt), _f(sums), W, T)
+        if n < 0:
+            raise QasrError(f"qasr_get_samples: {lib().qasr_last_error().decode(errors='replace')}")
+        return [Sample(toks[i, :nt[i]].tolist(), lps[i, :nt[i]].tolist(), float(sums[i])) for i in range(n)]
+
+    def _sampling_on(self) -> bool:
+        return self.get_sampling().temperature > 0 and not self.model.is_aligner
+
+    def _run_result(self, toks, nt, t, max_tokens: int) -> RunResult:
+        B = len(nt)
+        tokens = [toks[b, :nt[b]].tolist() for b in range(B)]
+        if self._sampling_on():
+            many = self.get_sampling().n_best >= 2   # (the per-row readers are the n_best = 1 run's)
+            return RunResult(tokens, t, None if many else self._run_logprobs(nt, max_tokens),
+                             None if many else self._run_topk(nt, max_tokens), samples=[self.samples(b) for b in range(B)])
+        if self._beam_on():
+            return RunResult(tokens, t, beams=[self.beams(b) for b in range(B)])
+        return RunResult(tokens, t, self._run_logprobs(nt, max_tokens), self._run_topk(nt, max_tokens))
+
     def _beam_on(self) -> bool:
         return self.get_option("beam_width") >= 2 and not self.model.is_aligner
 
@@ -581,10 +640,7 @@ class Context:
         nt = np.zeros(B, np.int32)
         t = Timings()
         _check(lib().qasr_run(self.h, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)), "qasr_run")
-        if self._beam_on():
-            return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, beams=[self.beams(b) for b in range(B)])
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
-                         self._run_topk(nt, max_tokens))
+        return self._run_result(toks, nt, t, max_tokens)
 
     def _run_logprobs(self, nt, max_tokens: int):
         """the last run's log-probabilities per row (None with option token_logprobs off)"""
@@ -627,10 +683,7 @@ class Context:
         t = Timings()
         _check(lib().qasr_run_staged(self.h, _i(idx), B, max_tokens, int(ignore_eos), _i32(toks), _i(nt), C.byref(t)),
                "qasr_run_staged")
-        if self._beam_on():
-            return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, beams=[self.beams(b) for b in range(B)])
-        return RunResult([toks[b, :nt[b]].tolist() for b in range(B)], t, self._run_logprobs(nt, max_tokens),
-                         self._run_topk(nt, max_tokens))
+        return self._run_result(toks, nt, t, max_tokens)
 
     def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0, logprobs: bool = False,
                    topk: bool = False):
