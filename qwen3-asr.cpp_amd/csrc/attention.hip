@@ -1269,7 +1269,8 @@ int decode_stream_slots() {
 // wait is bounded so no order can hang the GPU.
 // Blocks past the attention splits (when att_done is set): the o-projection
 // (gemv1 arithmetic, K = 2048, one row per wave, + residual): weights
-// requested after a delay, a bounded wait for all kv groups' combiners
+// requested after a delay, a bounded wait for the arrivals of all kv groups'
+// combiners -- with exact attention of all heads' chain workgroups --
 // (att_done replica block % 8), then the fp16 attention output and the
 // residual row read with sc1 loads.  att_done is re-armed by the down-proj
 // launch that follows (GemvArgs.zero8).
@@ -1291,7 +1292,7 @@ __device__ __forceinline__ void oproj1_body(const GemvArgs o, const DecodeAttnAr
         int ok = 0;
         for (int it = 0; it < a.poll_limit; it++) {
             if (__hip_atomic_load(a.att_done + (j & 7) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >=
-                (unsigned)a.n_kv_head) {
+                (unsigned)(a.fx ? a.n_head : a.n_kv_head)) {   // a chain workgroup a head, or a combiner a kv group
                 ok = 1;
                 break;
             }
@@ -1327,162 +1328,135 @@ __device__ __forceinline__ void oproj1_body(const GemvArgs o, const DecodeAttnAr
 }
 
 // Chain role of the fused exact attention (DecodeAttnArgs.fx): one workgroup
-// per kv group g, wave w running query head 2g + w / 2, dimensions 64 (w % 2)
-// + lane, with ggml's CPU flash-attention numerics (fx_chain.h; the same
-// arithmetic as fa_exact.hip's decode_attn_exact_kernel, so the two launches
-// are bit-identical).  V^T of keys below the position comes from the cache
-// (earlier steps' rows; the first 128 keys requested at entry); the new key's
-// v from its QKV granule.  The two heads' scores arrive as granules from the
-// splits, gathered per DX_KC-key chunk into LDS (every thread polls its own
-// 16-B granule pairs, bounded); each wave derives the chunk's weights from
-// LDS into registers and runs the chain.  The output goes to the o-projection
-// role as the split-K combiners' does (write-through, drained, att_done).
-// eight 16-B sc1 loads at base + off[u] bytes (base uniform: the SGPR-pair
-// address form, so the offsets cost one VGPR each), drained in the same asm
-// block (no copy of an output can be scheduled before the data has landed)
-__device__ __forceinline__ void ld_sc1_x4_8(const void *base, const uint32_t *off, u32x4 *v) {
-    asm volatile(
-        "global_load_dwordx4 %0, %8, %16 sc1\n\t"
-        "global_load_dwordx4 %1, %9, %16 sc1\n\t"
-        "global_load_dwordx4 %2, %10, %16 sc1\n\t"
-        "global_load_dwordx4 %3, %11, %16 sc1\n\t"
-        "global_load_dwordx4 %4, %12, %16 sc1\n\t"
-        "global_load_dwordx4 %5, %13, %16 sc1\n\t"
-        "global_load_dwordx4 %6, %14, %16 sc1\n\t"
-        "global_load_dwordx4 %7, %15, %16 sc1\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-        : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), "v"(off[5]), "v"(off[6]), "v"(off[7]), "s"(base)
-        : "memory");
-}
-// chain workgroups of the fused launch: one a kv group (4 chain waves)
-__host__ __device__ inline int fx_chain_wgs(int fx, int n_kv_head) { return fx ? n_kv_head : 0; }
-// the chain role's LDS (fx1_chain_body: both heads): a layout of the fused
-// launch's shared role buffer
+// per query head, chain workgroup c serving head 2 (c % n_kv_head) + c /
+// n_kv_head of kv group c % n_kv_head (so it shares an XCD, and an L2, with
+// the group's splits), with ggml's CPU flash-attention numerics (fx_chain.h;
+// the same arithmetic as fa_exact.hip's decode_attn_exact_kernel, so the two
+// launches are bit-identical).  Waves 0 and 1 are the chain waves: dimensions
+// 64 w + lane, V^T of keys below the position from the cache (earlier steps'
+// rows), the new key's v from its QKV granule.  Waves 2 and 3 are the
+// producer waves: per chunk of FX_PC keys they poll the head's score granules
+// (bounded), derive the chunk's signed weights and new-maximum bits into LDS
+// carrying the running maximum from chunk to chunk, and publish the chunk
+// through an LDS progress word (both read the whole chunk and take the same
+// scan -- 2 KiB a chunk read twice -- so no LDS hop stands between them); after the last chunk one of them adds up S.
+// A chain wave tests the progress word once a chunk (bounded), so the chain
+// starts behind the first chunk's weights instead of behind all of them.
+// After the roles diverge no barrier stands before the one every wave reaches
+// at the hand-off.  The output goes to the o-projection role as the split-K
+// combiners' does (write-through, drained, att_done: one arrival a workgroup).
+// chain workgroups of the fused launch: one a query head (2 chain + 2 producer waves)
+__host__ __device__ inline int fx_chain_wgs(int fx, int n_head) { return fx ? n_head : 0; }
+// the chain role's LDS (one head): a layout of the fused launch's shared role
+// buffer
 struct alignas(16) ChainLds {
-    float fsc[2][DX_KC / DX_B * FX_ST];
-    uint16_t kmask[2][DX_KC / 16];
-    float fwl[2];
+    float fsc[DX_KC / DX_B * FX_ST];      // the signed weights, FX_ST floats per 32-key row (fx_w8)
+    uint16_t kmask[DX_KC / 16];           // new-maximum bit of every key
+    float gmax[DX_KC / DX_B];             // the maximum of keys 0 .. 32 r + 31 (S: the row's reference)
+    uint32_t prog[DX_KC / FX_PC + 1];     // per chunk: byte p = 0x80 | buffer bits once producer p has stored it; last: S stored
+    float fwl, S;                         // the new key's weight; the row sum
+    float vpf[4][256];                    // the L2 prefetch's LDS-DMA target, a KiB a wave (contents unused)
 };
-// Phases (1) and (2) of a chain workgroup holding both query heads of kv group
-// g (fx1_chain_body): the score granules of both heads -> LDS,
-// then wave wid the weights of head wid / 2, half wid % 2 (C.fsc, C.kmask,
-// C.fwl); returns that head's S.  n: keys (<= DX_KC); trow: its trace row.
-__device__ __forceinline__ float fx1_gather_weights(const DecodeAttnArgs &a, const int g, const int n, ChainLds &C, const int trow) {
-    auto &fsc = C.fsc;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int hh = wid >> 1, wu = __builtin_amdgcn_readfirstlane(wid & 1);
-    auto mark = [&](int slot) {
-        if (a.trace && tid == 0) a.trace[(long)trow * 8 + slot] = rt_now();
-    };
+constexpr uint32_t FX_PUB = 0x8080u;   // both producers' bytes of a progress word
+// The producer waves of a chain workgroup (p = 0, 1: uniform): the weights of
+// head `head`'s n keys (<= DX_KC) chunk by chunk into C.  Both waves read the
+// chunk's FX_PC scores, four keys a lane, and take the prefix maxima (exact and
+// order-free: every key's reference maximum is the one fx_weights_reg uses);
+// wave p computes the expf of keys 2 p, 2 p + 1 of every lane.  The new key
+// n - 1 gets weight 0 in LDS (a no-op for the chain loop, which reads the cache
+// row another workgroup is writing) and its weight in fwl, applied once after
+// the loop with vnew -- the same sequence of operations as fa_exact.hip's
+// chain, so both launches agree bit for bit.  tr: the workgroup's trace row.
+__device__ __forceinline__ void fx1_gather_weights(const DecodeAttnArgs &a, const int head, const int n, ChainLds &C, const int p,
+                                                   unsigned long long *tr) {
+    const int lane = threadIdx.x & 63;
     const uint32_t tag = gran_tag(a.pos[0], a.layer);
-    const int np = (n + 1) >> 1;
-    // (1) the score granules of both heads -> LDS: thread tid takes the 16-B
-    //     pairs q = tid + 256 (u / 2) of head u % 2, all in flight together
-    {
-        const int ld = sgran_ld(a.max_ctx);
-        const unsigned long long *gb = a.sgran + (long)(2 * g) * ld;   // uniform
-        uint32_t go[DX_KC / 256];
-#pragma unroll
-        for (int u = 0; u < DX_KC / 256; u++) {
-            const int q = tid + 256 * (u >> 1);
-            go[u] = q < np ? (uint32_t)(((u & 1) * ld + 2 * q) * 8) : 0u;
-        }
-        u32x4 gv[DX_KC / 256];
+    const unsigned long long *gb = a.sgran + (long)head * sgran_ld(a.max_ctx);   // uniform
+    unsigned char *pb = (unsigned char *)C.prog;   // (accessed as workgroup-scope atomics: plain LDS reads and writes the compiler keeps in place)
+    const int nch = (n + FX_PC - 1) / FX_PC, kl = n - 1;
+    float M = -INFINITY;
+    unsigned long long npoll = 0;
+    for (int ch = 0; ch < nch; ch++) {
+        // (1) the chunk's score granules: lane L polls keys 4 L .. 4 L + 3 (32
+        //     bytes; rows are padded to 64 keys, lanes past n re-read key 0)
+        const int k0 = ch * FX_PC + 4 * lane;
+        const unsigned long long *gp = gb + (k0 < n ? k0 : 0);
+        unsigned long long gv[4];
         bool ok = false;
-        int it = 0;
-        unsigned long long tis = 0;   // (trace) the last poll's issue time
-        for (; it < a.poll_limit; it++) {
-            if (a.trace) tis = rt_now();
-            ld_sc1_x4_8(gb, go, gv);
+        for (int it = 0; it < a.poll_limit; it++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) gv[e] = __hip_atomic_load(gp + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             ok = true;
 #pragma unroll
-            for (int u = 0; u < DX_KC / 256; u++) {
-                const int q = tid + 256 * (u >> 1);
-                if (q < np) ok = ok && gv[u][1] == tag && (2 * q + 1 >= n || gv[u][3] == tag);
-            }
-            if (__syncthreads_and(ok)) break;
+            for (int e = 0; e < 4; e++) ok = ok && (k0 + e >= n || (uint32_t)(gv[e] >> 32) == tag);
+            npoll++;
+            if (__all(ok)) break;
             __builtin_amdgcn_s_sleep(2);
         }
-        if (a.trace && tid == 0) {   // rows 4010 + g: polls, the successful poll's issue time
-            a.trace[(4010L + g) * 8 + 5] = (unsigned long long)it + 1;
-            a.trace[(4010L + g) * 8 + 6] = tis;
-        }
-        if (!ok && tid == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_SCORE_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!__all(ok) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_SCORE_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float sv[4];
 #pragma unroll
-        for (int u = 0; u < DX_KC / 256; u++) {
-            const int q = tid + 256 * (u >> 1), j = 2 * q;   // even: both keys in one 32-key row
-            if (q < np)
-                *(float2 *)&fsc[u & 1][(j >> 5) * FX_ST + (j & 31)] = make_float2(__uint_as_float(gv[u][0]), __uint_as_float(gv[u][2]));
+        for (int e = 0; e < 4; e++) sv[e] = k0 + e < n ? __uint_as_float((uint32_t)gv[e]) : -INFINITY;
+        // (2) the weights: exclusive prefix maximum over the lanes plus the
+        //     carry of the earlier chunks, then key by key within the lane
+        const float lh = fmaxf(sv[0], sv[1]);
+        const float lm = fmaxf(lh, fmaxf(sv[2], sv[3]));
+        const float inc = wave_scan_max(lm);
+        const float Mp0 = fmaxf(M, dpp_ninf<0x138, 0xF>(inc));   // wave_shr:1 (lane 0: the carry)
+        const float Mi = fmaxf(M, inc);
+        M = fmaxf(M, lane_f(inc, 63));
+        uint32_t kb = 0;
+        {
+            float Mq = Mp0;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                kb |= (uint32_t)(sv[e] > Mq) << e;
+                Mq = fmaxf(Mq, sv[e]);
+            }
+        }
+        float x0, x1;
+        fx_weights2(p ? fmaxf(Mp0, lh) : Mp0, p ? sv[2] : sv[0], p ? sv[3] : sv[1], x0, x1);
+        const int k = k0 + 2 * p;   // even: both keys in one 32-key row
+        if (k == kl) { C.fwl = x0; x0 = 0.0f; }
+        if (k + 1 == kl) { C.fwl = x1; x1 = 0.0f; }
+        *(float2 *)&C.fsc[(k >> 5) * FX_ST + (k & 31)] = make_float2(x0, x1);
+        uint32_t m16 = kb << (4 * (lane & 3));   // 16 keys = 4 lanes: the slow path's 8-key groups
+        m16 |= __shfl_xor(m16, 1, 64);
+        m16 |= __shfl_xor(m16, 2, 64);
+        const uint32_t bits = fx_chunk_bits(kb);
+        if (p == 0) {
+            if ((lane & 3) == 0) C.kmask[ch * (FX_PC / 16) + (lane >> 2)] = (uint16_t)m16;
+            if ((lane & 7) == 7) C.gmax[ch * (FX_PC / DX_B) + (lane >> 3)] = Mi;
+        }
+        // (3) publish: the stores above have completed before the progress byte goes out
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if (lane == 0) __hip_atomic_store(pb + 4 * ch + p, (unsigned char)(0x80u | bits), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (tr && p == 0 && lane == 0 && (ch == 0 || ch == nch - 1)) {
+            if (ch == 0) tr[2] = rt_now();
+            if (ch == nch - 1) tr[3] = rt_now();
         }
     }
-    __syncthreads();
-    mark(2);
-    // (2) the weights of this wave's head, fx_weights_reg's arithmetic split
-    //     over the head's two waves: both read the lane's 32 scores and take
-    //     the maxima (a lane's batch holds a new maximum iff its maximum beats
-    //     the exclusive prefix), wave wu computes the expf of keys 16 wu ..
-    //     16 wu + 15 of every lane and writes them back over the scores.  The
-    //     new key n - 1 gets weight 0 in LDS (a no-op for the chain loop, which
-    //     reads the cache row another workgroup is writing) and its weight in
-    //     fwl, applied once after the loop with vnew -- the same sequence of
-    //     operations as fa_exact.hip's chain, so both launches agree bit for bit
-    auto &fwl = C.fwl;
-    auto &kmask = C.kmask;   // per head: new-maximum bit of every key
-    float M, S;
+    if (p != 0) return;
+    // (4) S with fx_weights_reg's grouping, off the chain's way in: lane L the
+    //     sequential S = S * ms + vs over keys 32 L .. 32 L + 31 read back from
+    //     LDS (key n - 1 read as 0 is S * 1 + 0 = S: its own term, the lane's
+    //     last, goes after), scaled to the final maximum, summed over the wave.
+    //     Rows past the last chunk were never written: their term is the 0.0f
+    //     that 32 zero weights give.  The other producer's bytes first (bounded)
     {
-        float *row = fsc[hh] + lane * FX_ST;   // this lane's 32 keys
-        float sv[DX_B];
-#pragma unroll
-        for (int i = 0; i < DX_B; i += 4) {
-            const floatx4 r = *(const floatx4 *)&row[i];
-#pragma unroll
-            for (int e = 0; e < 4; e++) sv[i + e] = lane * DX_B + i + e < n ? r[e] : -INFINITY;
+        uint32_t w = 0;
+        for (int it = 0; it < a.poll_limit; it++) {
+            w = __hip_atomic_load(pb + 4 * (nch - 1) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (w & 0x80u) break;
+            __builtin_amdgcn_s_sleep(1);
         }
-        float lm = -INFINITY, lh = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < DX_B / 2; i++) lh = fmaxf(lh, sv[i]);
-#pragma unroll
-        for (int i = DX_B / 2; i < DX_B; i++) lm = fmaxf(lm, sv[i]);
-        lm = fmaxf(lm, lh);
-        const float inc = wave_scan_max(lm);
-        const float Mp0 = dpp_ninf<0x138, 0xF>(inc);   // exclusive prefix (lane 0: -inf; the chunk is the first)
-        M = lane_f(inc, 63);
-        float x[DX_B / 2];
-        uint32_t kb = 0;
-        // the wave's half of the lane's keys, indexed statically in each branch
-        // (a select on wu became a wu-offset index into sv, which put sv in
-        // scratch memory: a global-memory round trip before the chain)
-        auto half = [&](auto hc) {
-            constexpr int H = decltype(hc)::value;
-            float Mq = H ? fmaxf(Mp0, lh) : Mp0;
-#pragma unroll
-            for (int i = 0; i < DX_B / 2; i++) {
-                const float sc = sv[H * (DX_B / 2) + i];
-                const bool gt = sc > Mq;
-                const float e = expf(gt ? Mq - sc : sc - Mq);
-                x[i] = gt ? -e : (sc != -INFINITY ? e : 0.0f);
-                kb |= (uint32_t)gt << i;
-                Mq = fmaxf(Mq, sc);
-            }
-        };
-        if (wu) half(std::integral_constant<int, 1>{});
-        else half(std::integral_constant<int, 0>{});
-        kmask[hh][2 * lane + wu] = (uint16_t)kb;   // keys 32 lane + 16 wu ..: the slow path's 8-key groups
-        __syncthreads();   // both waves have read their scores
-        mark(6);
-#pragma unroll
-        for (int i = 0; i < DX_B / 2; i += 4) *(floatx4 *)&row[16 * wu + i] = floatx4{x[i], x[i + 1], x[i + 2], x[i + 3]};
-        const int kl = n - 1;
-        if (lane == (kl >> 5) && wu == ((kl >> 4) & 1)) {   // (its own store above: ordered)
-            fwl[hh] = row[kl & 31];
-            row[kl & 31] = 0.0f;
-        }
-        __syncthreads();
-        mark(7);
-        // the lane's sequential S = S * ms + vs over its 32 weights (key n - 1
-        // read as 0 is S * 1 + 0 = S: its own term, the lane's last, goes after)
-        const float wl = fwl[hh];
+        if (!(w & 0x80u) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_SCORE_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    float term = 0.0f;
+    if (lane * DX_B < nch * FX_PC) {
+        const float *row = C.fsc + lane * FX_ST;
+        const float wl = C.fwl;
         float Sl = 0.0f;
 #pragma unroll
         for (int i = 0; i < DX_B; i += 4) {
@@ -1491,128 +1465,183 @@ __device__ __forceinline__ float fx1_gather_weights(const DecodeAttnArgs &a, con
             for (int e = 0; e < 4; e++) Sl = __builtin_signbit(r[e]) ? fadd_rn(fmul_rn(Sl, -r[e]), 1.0f) : fadd_rn(fmul_rn(Sl, 1.0f), r[e]);
         }
         if (lane == (kl >> 5)) Sl = __builtin_signbit(wl) ? fadd_rn(fmul_rn(Sl, -wl), 1.0f) : fadd_rn(fmul_rn(Sl, 1.0f), wl);
-        const float Ml = fmaxf(Mp0, lm);
-        S = wave_sum(Ml == -INFINITY ? 0.0f : Sl * expf(Ml - M));
+        const float Ml = C.gmax[lane];
+        term = Ml == -INFINITY ? 0.0f : Sl * expf(Ml - M);
     }
-    return S;
+    const float S = wave_sum(term);
+    if (lane == 0) C.S = S;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(&C.prog[DX_KC / FX_PC], FX_PUB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (tr && lane == 0) {
+        tr[6] = rt_now();
+        tr[7] = npoll;
+    }
 }
-__device__ __forceinline__ void fx1_chain_body(const DecodeAttnArgs &a, const int g, ChainLds &C) {
-    auto &fsc = C.fsc;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int hh = wid >> 1, wu = __builtin_amdgcn_readfirstlane(wid & 1);
+// a chain wave's bounded wait for progress word i of C (both producers'
+// bytes); returns the word (uniform).  The wait that runs out reports
+// DEVERR_SCORE_WAIT and the wave goes on with what LDS holds
+__device__ __forceinline__ uint32_t fx1_progress(const DecodeAttnArgs &a, ChainLds &C, const int i) {
+    const uint32_t *pw = &C.prog[i];
+    uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    if (__builtin_expect((w & FX_PUB) != FX_PUB, 0)) {
+        for (int it = 0; it < a.poll_limit; it++) {
+            __builtin_amdgcn_s_sleep(1);
+            w = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            if ((w & FX_PUB) == FX_PUB) break;
+        }
+        if ((w & FX_PUB) != FX_PUB && (threadIdx.x & 63) == 0)
+            __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_SCORE_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return w;
+}
+__device__ __forceinline__ void fx1_chain_body(const DecodeAttnArgs &a, const int c, ChainLds &C) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = c % a.n_kv_head, hh = c / a.n_kv_head, head = 2 * g + hh;
+    const int wu = wid & 1;   // the chain waves' dimension half; the prefetch's of every wave
     const int d = 64 * wu + lane, loff = 8 * lane;
     const uint16_t *vt = a.vt + (long)g * 128 * vt_ctx(a.max_ctx) + 64 * wu * 8;   // batch 1: slot 0; the wave's key block 0
-    // dev trace (QASR_DEV_TRACE): rows 4000 + g of the attention kernel's table:
-    // [start, v ready, scores gathered, weights done, chain done, published,
-    //  weights: expf pass done, weights stored]
-    // (v ready comes after the weights: the new v is polled last)
+    // dev trace (QASR_DEV_TRACE), the attention kernel's table: row 4000 + c =
+    // [start, chain start, first chunk published, last chunk published, chain
+    //  done, published, S done, producer 0's polls]; row 4040 + c = [shader
+    // clock at chain start, at its end, keys, new-maximum keys, slow 8-key
+    // groups]; row 4080 + c = chain wave w's end (100 MHz) at w, its shader
+    // cycles at 2 + w
+    unsigned long long *tr = a.trace ? a.trace + (4000L + c) * 8 : nullptr;
     auto mark = [&](int slot) {
-        if (a.trace && tid == 0) a.trace[(4000L + g) * 8 + slot] = rt_now();
+        if (tr && tid == 0) tr[slot] = rt_now();
     };
     mark(0);
-    const int pos = a.pos[0], nkv = pos + 1;
-    const uint32_t tag = gran_tag(pos, a.layer);
-    const int QD = a.n_head * 128, KD = a.n_kv_head * 128;
-    // V^T of the wave's 64 dimensions -> this CU's L2 while the scores are
-    // computed: wave w pulls the key blocks kb = w / 2 (mod 2), so the four
-    // waves cover their two dimension halves once; LDS-DMA pieces (no
-    // register destination) into the wave's own 1 KiB of fsc, contents unused
-    // (the first gather poll below drains them: its vmcnt(0) and barrier).
-    // Without it the chain's V^T loads were HBM misses one 64-key buffer
-    // ahead: ~40 cycles a key instead of ~12 (device trace, layer 14).
+    const int pos = a.pos[0], n = pos + 1;   // one weights image: the launch is taken only while n_kv <= DX_KC (launch_qkv_attention1)
+    if (tid <= DX_KC / FX_PC) C.prog[tid] = 0u;
+    // V^T of the head's 128 dimensions -> this XCD's L2 while the scores are
+    // computed: wave w pulls the key blocks kb = w / 2 (mod 2) of dimension
+    // half w % 2, so the four waves cover the workgroup's dimensions once;
+    // LDS-DMA pieces (no register destination) into the wave's own KiB of
+    // vpf, contents unused.  Without it the chain's V^T loads were HBM misses
+    // one 64-key buffer ahead: ~40 cycles a key instead of ~12 (device trace,
+    // layer 14).  (The kv group's other head pulls the same bytes from its
+    // own CU: whichever comes second hits the L2.)
     if (a.fx_vpf & 2) {
         typedef __attribute__((address_space(3))) void lds_void_c;
         typedef __attribute__((address_space(1))) void glb_void_c;
-        lds_void_c *dst = (lds_void_c *)((float *)fsc + wid * 256);
-        for (int kb = hh; kb * 8 < nkv; kb += 2)
+        lds_void_c *dst = (lds_void_c *)C.vpf[wid];
+        for (int kb = wid >> 1; kb * 8 < n; kb += 2)
             __builtin_amdgcn_global_load_lds((glb_void_c *)(vt + (long)kb * 1024 + loff), dst, 16, 0, 0);
     }
-    // one chunk: the launch is taken only while n_kv <= DX_KC (launch_qkv_attention1)
-    const int n = nkv;
-    const float S = fx1_gather_weights(a, g, n, C, 4000 + g);
-    auto &fwl = C.fwl;
-    auto &kmask = C.kmask;   // per head: new-maximum bit of every key
-    mark(3);
-    // the new key's v (this lane's dimension): its QKV granule, cast to fp16 as
-    // the cache write is (long published by now: polled after the weights)
-    uint16_t vnew = 0;
-    {
-        const unsigned long long *gp = a.gran + QD + KD + g * 128 + d;
-        unsigned long long v = 0;
-        bool ok = false;
-        for (int it = 0; it < a.poll_limit; it++) {
-            v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = (uint32_t)(v >> 32) == tag;
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (!__all(ok) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_QKV_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        vnew = f_to_u16(__uint_as_float((uint32_t)v));
-    }
-    mark(1);
-    // (trace) shader clock against the 100 MHz counter over the chain: row 4010 + g
-    const unsigned long long ck0 = a.trace ? clock64() : 0ull;
-    f16 acc = 0;
-    {
-        // keys 0 .. n - 2 from V^T in 64-key steps (the last may run into key
-        // n - 1 and past n: zero weights in fsc), then the new key
+    __syncthreads();   // the progress words are zero; the last barrier before the hand-off's
+    if (wid >= 2) {
+        fx1_gather_weights(a, head, n, C, wid - 2, tr);
+    } else {
+        const uint32_t tag = gran_tag(pos, a.layer);
+        const int QD = a.n_head * 128, KD = a.n_kv_head * 128;
+        const float *fsc = C.fsc;
+        const uint16_t *kmask = C.kmask;
         const int nl = n - 1;
-        u32x4 va[DX_Q / 8], vb[DX_Q / 8];
-        floatx4 wa, wb;
-        const int lastb = nl > 0 ? (nl - 1) >> 3 : 0;
-        // buffers 0 .. nfull - 1 lie wholly at or below lastb: the main loop
-        // requests those (the two after the one it starts on) unclamped
-        // (fx_loadQ_sb: 16 KiB a buffer in the scalar offset), two buffers an
-        // iteration; the tail -- the clamped loop, at most three buffers --
-        // runs the rest, so the loads issued and the blocks they read are
-        // those of one clamped loop.  A wave alone on its SIMD pays ~4 cycles
-        // of issue per instruction of any kind: an all-fast buffer of the
-        // main loop is the 128 chain instructions + 45 others, of the tail
-        // 128 + ~90 (tools/chain_loop_count.py)
-        const int nfull = nl > 0 ? (lastb + 1) >> 3 : 0;
-        constexpr uint32_t QB = DX_Q / 8 * 2048;   // bytes between two buffers' key blocks
-        // (the wave's bytes of V^T: 1 KiB of each 2 KiB key block, up to block lastb's)
-        const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void *)vt, (short)0, lastb * 2048 + 1024, 0x00020000);
-        const uint32_t voff = 16 * lane;
-        int jt = 0;
-        fx_loadQ(va, vt, loff, 0, lastb);
-        fx_w8(fsc[hh], 0, wa, wb);
-        // which buffers hold a new maximum, one bit each (kmask is complete:
-        // two barriers since its stores); shifted down two bits an iteration
-        uint32_t bm = fx_buffer_bits(kmask[hh]);
-        for (; jt + 2 * DX_Q < nfull * DX_Q; jt += 2 * DX_Q, bm >>= 2) {
-            fx_loadQ_sb(vb, vrs, voff, (jt / DX_Q + 1) * QB);
-            fx_step1_lds_b(va, jt, fsc[hh], kmask[hh], bm & 1u, acc, wa, wb);
-            fx_loadQ_sb(va, vrs, voff, (jt / DX_Q + 2) * QB);
-            fx_step1_lds_b(vb, jt + DX_Q, fsc[hh], kmask[hh], bm & 2u, acc, wa, wb);
+        if (a.trace && nl > 0) {   // (trace) the chain's start = the first chunk's weights are there
+            (void)fx1_progress(a, C, 0);
+            mark(1);
         }
-        for (int j0 = jt; j0 < nl; j0 += 2 * DX_Q, bm >>= 2) {
-            fx_loadQ(vb, vt, loff, j0 + DX_Q, lastb);
-            fx_step1_lds_b(va, j0, fsc[hh], kmask[hh], bm & 1u, acc, wa, wb);
-            if (j0 + DX_Q >= nl) break;
-            fx_loadQ(va, vt, loff, j0 + 2 * DX_Q, lastb);
-            fx_step1_lds_b(vb, j0 + DX_Q, fsc[hh], kmask[hh], bm & 2u, acc, wa, wb);
+        // (trace) shader clock against the 100 MHz counter over the chain: row 4040 + c
+        const unsigned long long ck0 = a.trace ? clock64() : 0ull;
+        f16 acc = 0;
+        {
+            // keys 0 .. n - 2 from V^T in 64-key steps (the last may run into key
+            // n - 1 and past n: zero weights in fsc), then the new key
+            u32x4 va[DX_Q / 8], vb[DX_Q / 8];
+            floatx4 wa, wb;
+            const int lastb = nl > 0 ? (nl - 1) >> 3 : 0;
+            // buffers 0 .. nfull - 1 lie wholly at or below lastb: the main loop
+            // requests those (the two after the one it starts on) unclamped
+            // (fx_loadQ_sb: 16 KiB a buffer in the scalar offset), two buffers an
+            // iteration; the tail -- the clamped loop, at most three buffers --
+            // runs the rest, so the loads issued and the blocks they read are
+            // those of one clamped loop.  A wave alone on its SIMD pays ~4 cycles
+            // of issue per instruction of any kind: an all-fast buffer of the
+            // main loop is the 128 chain instructions + 47.5 others (+ 11 a
+            // chunk for the progress test), of the tail 128 + 96 (tools/chain_loop_count.py)
+            const int nfull = nl > 0 ? (lastb + 1) >> 3 : 0;
+            constexpr uint32_t QB = DX_Q / 8 * 2048;   // bytes between two buffers' key blocks
+            // (the wave's bytes of V^T: 1 KiB of each 2 KiB key block, up to block lastb's)
+            const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void *)vt, (short)0, lastb * 2048 + 1024, 0x00020000);
+            const uint32_t voff = 16 * lane;
+            int jt = 0;
+            fx_loadQ(va, vt, loff, 0, lastb);
+            // which of the chunk's buffers hold a new maximum: the low bits of
+            // its progress word, read on entering the chunk (every other
+            // iteration) after the next buffer's loads are out, and shifted
+            // down two bits an iteration.  The weights of the chunk's first
+            // eight keys are read behind that test, not ahead of it
+            uint32_t bm = 0;
+            const float *wrow = fsc;         // the iteration's first weights row and masks: carried, not
+            const uint16_t *krow = kmask;    // recomputed from jt three times an iteration
+            for (; jt + 2 * DX_Q < nfull * DX_Q; jt += 2 * DX_Q, bm >>= 2, wrow += 2 * DX_Q / DX_B * FX_ST, krow += 2 * DX_Q / 16) {
+                fx_loadQ_sb(vb, vrs, voff, (jt / DX_Q + 1) * QB);
+                if ((jt & (FX_PC - 1)) == 0) {
+                    bm = fx1_progress(a, C, jt / FX_PC);
+                    fx_w8(wrow, 0, wa, wb);
+                }
+                fx_step1_lds_b(va, 0, wrow, krow, bm & 1u, acc, wa, wb);
+                fx_loadQ_sb(va, vrs, voff, (jt / DX_Q + 2) * QB);
+                fx_step1_lds_b(vb, DX_Q, wrow, krow, bm & 2u, acc, wa, wb);
+            }
+            for (int j0 = jt; j0 < nl; j0 += 2 * DX_Q, bm >>= 2) {
+                fx_loadQ(vb, vt, loff, j0 + DX_Q, lastb);
+                if ((j0 & (FX_PC - 1)) == 0) {
+                    bm = fx1_progress(a, C, j0 / FX_PC);
+                    fx_w8(fsc, j0, wa, wb);
+                }
+                fx_step1_lds_b(va, j0, fsc, kmask, bm & 1u, acc, wa, wb);
+                if (j0 + DX_Q >= nl) break;
+                fx_loadQ(va, vt, loff, j0 + 2 * DX_Q, lastb);
+                fx_step1_lds_b(vb, j0 + DX_Q, fsc, kmask, bm & 2u, acc, wa, wb);
+            }
         }
-        acc = fx_key_slow(acc, vnew, fwl[hh]);
+        const unsigned long long ck1 = a.trace ? clock64() : 0ull;
+        // the new key's v (this lane's dimension): its QKV granule, cast to fp16
+        // as the cache write is (long published by now: polled after the loop)
+        uint16_t vnew = 0;
+        {
+            const unsigned long long *gp = a.gran + QD + KD + g * 128 + d;
+            unsigned long long v = 0;
+            bool ok = false;
+            for (int it = 0; it < a.poll_limit; it++) {
+                v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok = (uint32_t)(v >> 32) == tag;
+                if (__all(ok)) break;
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (!__all(ok) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_QKV_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            vnew = f_to_u16(__uint_as_float((uint32_t)v));
+        }
+        // S and the new key's weight: stored by now (the producers were done
+        // ~2 us into a ~10 us chain), behind the last progress word all the same
+        (void)fx1_progress(a, C, DX_KC / FX_PC);
+        const float S = C.S;
+        acc = fx_key_slow(acc, vnew, C.fwl);
+        mark(4);
+        if (a.trace && lane == 0) {
+            a.trace[(4080L + c) * 8 + wid] = rt_now();
+            a.trace[(4080L + c) * 8 + 2 + wid] = ck1 - ck0;
+        }
+        if (a.trace && tid == 0) {
+            a.trace[(4040L + c) * 8 + 0] = ck0;
+            a.trace[(4040L + c) * 8 + 1] = ck1;
+            a.trace[(4040L + c) * 8 + 2] = (unsigned long long)n;
+        }
+        // ggml: VKQ32 = fp32(VKQ16) * (1 / S); fp16 for the o-projection
+        const float ov = (float)acc * (S == 0.0f ? 0.0f : 1.0f / S);
+        const uint32_t h16 = f_to_u16(ov);
+        const uint32_t hn = __shfl_xor(h16, 1, 64);
+        uint16_t *out = a.out + head * 128 + d;
+        if (a.att_done) {   // the o-proj blocks of this launch read it: write-through pairs, drained below
+            if ((lane & 1) == 0) __hip_atomic_store((uint32_t *)out, h16 | (hn << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+            *out = (uint16_t)h16;
+        }
     }
-    mark(4);
-    if (a.trace && lane == 0) {   // every wave: its chain's end (100 MHz) and shader cycles, rows 4020 + g, 4030 + g
-        a.trace[(4020L + g) * 8 + wid] = rt_now();
-        a.trace[(4030L + g) * 8 + wid] = clock64() - ck0;
-    }
-    if (a.trace && tid == 0) {
-        a.trace[(4010L + g) * 8 + 0] = ck0;
-        a.trace[(4010L + g) * 8 + 1] = clock64();
-        a.trace[(4010L + g) * 8 + 2] = (unsigned long long)n;
-    }
-    // ggml: VKQ32 = fp32(VKQ16) * (1 / S); fp16 for the o-projection
-    const float ov = (float)acc * (S == 0.0f ? 0.0f : 1.0f / S);
-    const uint32_t h16 = f_to_u16(ov);
-    const uint32_t hn = __shfl_xor(h16, 1, 64);
-    uint16_t *out = a.out + (2 * g + hh) * 128 + d;
-    if (a.att_done) {   // the o-proj blocks of this launch read it: write-through pairs, drained, one arrival per replica
-        if ((lane & 1) == 0) __hip_atomic_store((uint32_t *)out, h16 | (hn << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (a.att_done) {   // every wave: the chain waves' output has landed, then one arrival per replica
         __syncthreads();
         if (a.fence && tid == 0) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1620,19 +1649,17 @@ __device__ __forceinline__ void fx1_chain_body(const DecodeAttnArgs &a, const in
         }
         if (a.fence) __syncthreads();
         if (tid < 8) __hip_atomic_fetch_add(a.att_done + tid * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        *out = (uint16_t)h16;
     }
     mark(5);
-    if (a.trace && tid == 0) {   // (after the hand-off: one thread's 128 LDS reads took ~5 us before it)
-        unsigned nk = 0, ng = 0;   // head 2g's new-maximum keys and slow 8-key groups
-        for (int i = 0; i < DX_KC / 16; i++) {
-            const unsigned m = kmask[0][i];
+    if (a.trace && tid == 0) {   // (after the hand-off: one thread's LDS reads took ~5 us before it)
+        unsigned nk = 0, ng = 0;   // the head's new-maximum keys and slow 8-key groups
+        for (int i = 0; i < (n + FX_PC - 1) / FX_PC * (FX_PC / 16); i++) {
+            const unsigned m = C.kmask[i];
             nk += __builtin_popcount(m);
             ng += ((m & 0xffu) != 0) + ((m >> 8) != 0);
         }
-        a.trace[(4010L + g) * 8 + 3] = nk;
-        a.trace[(4010L + g) * 8 + 4] = ng;
+        a.trace[(4040L + c) * 8 + 3] = nk;
+        a.trace[(4040L + c) * 8 + 4] = ng;
     }
 }
 
@@ -1646,11 +1673,11 @@ __global__ __launch_bounds__(256) void qkv_attn1_kernel(GemvArgs q, DecodeAttnAr
     stamp_start(a.stamp);
     if (blockIdx.x >= 512) {
         // splits (kv group j % n_kv_head: blocks b and b + 8 share an XCD under
-        // round-robin placement, so a group's splits and its chain workgroup
+        // round-robin placement, so a group's splits and its two chain workgroups
         // share one L2 -- speed only), the chain workgroups (exact attention),
         // the o-projection
         const int j = blockIdx.x - 512, nsp = a.grid_splits, nat = nsp * a.n_kv_head;   // grid_splits: this launch's splits
-        const int nfx = fx_chain_wgs(a.fx, a.n_kv_head);
+        const int nfx = fx_chain_wgs(a.fx, a.n_head);
         if (j >= nat + nfx) oproj1_body(o, a, j - nat - nfx);
         else if (j >= nat) fx1_chain_body(a, j - nat, *reinterpret_cast<ChainLds *>(role_lds));
         else decode_attn_body<SPL, true>(a, j / a.n_kv_head, j % a.n_kv_head, 0, nsp, *reinterpret_cast<SplitLds<SPL> *>(role_lds));
@@ -1764,13 +1791,15 @@ int launch_qkv_attention1(const GemvArgs &q, const DecodeAttnArgs &a, const Gemv
                         !o->Wd && !o->bias && !o->norm_w && o->xh == a.out;
     // every block of the launch must be co-resident (blocks wait on earlier
     // ones): fall back to separate launches for contexts that would not fit
-    // (exact attention: n_kv_head chain workgroups too; they read the new v
+    // (exact attention: n_head chain workgroups too; they read the new v
     // from its granule, so the fused exact path needs the granule hand-off)
-    // (fx_chain.h: one chain chunk)
+    // (fx_chain.h: the keys of one DX_KC weights image)
     if (a.fx && (!a.gran || !a.sgran || ns * spl1 > DX_KC)) return 0;
-    const int nfx = fx_chain_wgs(a.fx, a.n_kv_head);
+    const int nfx = fx_chain_wgs(a.fx, a.n_head);
     const int slots = spl1 == 128 ? cfg.slots_qkv128 : cfg.slots_qkv64;
     const int o_blocks = 1024 / OPROJ_ROWS;
+    // (with 16 chain workgroups the o-projection fits up to 30 splits of 1024 slots, one fewer
+    // than with 8: only a 64-key split forced past 1920 keys reaches that; the default takes 128-key splits there)
     const bool fit_o = 512 + ns * a.n_kv_head + nfx + o_blocks <= slots;
     if (512 + ns * a.n_kv_head + nfx > slots) return 0;
     const bool with_o2 = with_o && fit_o;

@@ -279,12 +279,28 @@ __device__ __forceinline__ void fx_step1_lds_b(const u32x4 *v, int j0, const flo
         }
     }
 }
-// bit b = keys 64 b .. 64 b + 63 hold a new maximum (km: the head's DX_KC / 16
-// u16 masks, complete; uniform result): lane b reads buffer b's four masks
-__device__ __forceinline__ uint32_t fx_buffer_bits(const uint16_t *km) {
-    static_assert(DX_KC / DX_Q == 32, "one bit a buffer in 32 bits");
-    const uint2 m = *(const uint2 *)(km + 4 * (threadIdx.x & 31));
-    return (uint32_t)__ballot((m.x | m.y) != 0u);   // (lanes 32 .. 63 repeat 0 .. 31: the upper half is dropped)
+// The fused launch's chain role produces its weights in chunks of FX_PC keys
+// (four DX_Q buffers), four keys a lane: lane L of a producer wave holds keys
+// 4 L .. 4 L + 3 of the chunk.  bit b of the result = the chunk's buffer b
+// (lanes 16 b .. 16 b + 15) holds a new maximum (kb4: the lane's four
+// new-maximum bits; uniform result)
+#define FX_PC 256
+__device__ __forceinline__ uint32_t fx_chunk_bits(uint32_t kb4) {
+    static_assert(FX_PC == 4 * 64 && FX_PC / DX_Q == 4, "four keys a lane, four buffers a chunk");
+    const unsigned long long bl = __ballot(kb4 != 0u);
+    return (uint32_t)((bl & 0xffffull) != 0) | (uint32_t)(((bl >> 16) & 0xffffull) != 0) << 1 |
+           (uint32_t)(((bl >> 32) & 0xffffull) != 0) << 2 | (uint32_t)((bl >> 48) != 0) << 3;
+}
+// the signed weights (header) of keys s0, s1 that follow a prefix maximum Mq,
+// fx_weights_reg's arithmetic: one expf per key, a new maximum stored as -ms
+__device__ __forceinline__ void fx_weights2(float Mq, float s0, float s1, float &x0, float &x1) {
+    const bool g0 = s0 > Mq;
+    const float e0 = expf(g0 ? Mq - s0 : s0 - Mq);
+    x0 = g0 ? -e0 : (s0 != -INFINITY ? e0 : 0.0f);
+    Mq = fmaxf(Mq, s0);
+    const bool g1 = s1 > Mq;
+    const float e1 = expf(g1 ? Mq - s1 : s1 - Mq);
+    x1 = g1 ? -e1 : (s1 != -INFINITY ? e1 : 0.0f);
 }
 
 // DX_Q keys of V for a buffer that lies wholly at or below the sequence's last

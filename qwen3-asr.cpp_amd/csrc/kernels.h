@@ -402,9 +402,9 @@ struct DecodeAttnArgs {
     int fx_seq;                          // decode batches on the per-sequence kernel: exact attention in one launch (FuseCfg::fx_seq)
     // batch-1 fused launch with ggml's fp16-accumulating attention (fx = 1,
     // needs gran): the splits publish their scaled scores as {fp32, tag}
-    // granules in sgran [n_head][max_ctx]; one chain workgroup per kv group
-    // runs fx_chain.h's chain for both query heads and hands the output to the
-    // o-projection role (att_done)
+    // granules in sgran [n_head][max_ctx]; one chain workgroup per query head
+    // (two producer waves for the weights, two chain waves running
+    // fx_chain.h's chain) hands the output to the o-projection role (att_done)
     int fx;
     unsigned long long *sgran;           // row stride sgran_ld(max_ctx) (16-B aligned granule pairs)
     int fx_vpf;                          // bit 0: the splits pull their keys' V^T rows into their XCD's L2 for the

@@ -9,11 +9,16 @@ NAMES = ["qkv_gemv", "attention", "oproj_gemv", "gateup_gemv", "down_gemv"]
 
 def main(path):
     t = np.fromfile(path, dtype=np.uint64).reshape(6, 4096, 8).astype(np.int64)
-    wide = (t[1][4040:4072, 0] > 0).any()   # fx_pipe 2, 3, 4: chain blocks c = 0 .. 31 at rows 4000 + c, clocks at 4040 + c
+    # chain workgroups.  Pipelined role (one workgroup a query head): rows 4000 + c = [start, chain start,
+    # first chunk published, last chunk published, chain done, published, S done, producer polls], 4040 + c =
+    # shader clock at chain start / end, keys, new-maximum keys, slow groups, 4080 + c = the two chain waves'
+    # ends and cycles.  Before it (one workgroup a kv group): rows 4000 + g, clocks at 4010 + g
+    wide = (t[1][4040:4072, 0] > 0).any()
     ch = t[1][4000:4040] if wide else t[1][4000:4008]
     ch = ch[ch[:, 0] > 0]
-    ck = (t[1][4040:4072] if wide else t[1][4010:4018]).copy()   # chain workgroups: shader clock at chain start / end, keys
-    t[1][4000:4080] = 0
+    ck = (t[1][4040:4072] if wide else t[1][4010:4018]).copy()
+    wv = t[1][4080:4096].copy()
+    t[1][4000:4096] = 0
     live = [t[k][t[k][:, 0] > 0] for k in range(5)]
     t0 = min(int(x[:, 0].min()) for x in live if len(x))
     us = lambda v: (v - t0) / 100.0
@@ -25,8 +30,12 @@ def main(path):
         if k == 1 and len(ch):   # fused exact attention: split blocks (scores) + chain workgroups
             print(f"{NAMES[k]:12s} split blocks {len(x):4d} start {us(st.min()):7.2f}..{us(st.max()):7.2f}  "
                   f"scores published max {us(x[:, 3].max()):7.2f}")
-            lab = ["start", "v ready", "scores gathered", "weights", "chain", "published", "w expf", "w stored"]
-            nl = 8 if (ch[:, 6] > 0).all() else 6
+            if wide:
+                lab = ["start", "chain start", "first chunk", "last chunk", "chain", "published", "S done"]
+                nl = 7
+            else:
+                lab = ["start", "v ready", "scores gathered", "weights", "chain", "published", "w expf", "w stored"]
+                nl = 8 if (ch[:, 6] > 0).all() else 6
             print(f"{'':12s} chain wgs {len(ch)}: " + "  ".join(f"{lab[i]} {us(np.median(ch[:, i])):6.2f}/{us(ch[:, i].max()):6.2f}"
                                                              for i in range(nl)))
             e = ch[:, 5].max()
@@ -36,7 +45,11 @@ def main(path):
                 dt = (ch[:, 4] - ch[:, 1]).astype(np.float64) / 100.0   # us, 'v ready' -> 'chain'
                 print(f"{'':12s} chain: {np.median(cyc):.0f} shader cycles over {ck[ok, 2][0]} keys "
                       f"({np.median(cyc) / ck[ok, 2][0]:.1f} a key), {np.median(dt):.2f} us -> {np.median(cyc / dt) / 1e3:.2f} GHz; "
-                      f"head 2g new-maximum keys {ck[ok, 3].tolist()}, slow 8-key groups {ck[ok, 4].tolist()}")
+                      f"{'per head' if wide else 'head 2g'} new-maximum keys {ck[ok, 3].tolist()}, slow 8-key groups {ck[ok, 4].tolist()}")
+                if wide:
+                    w2 = wv[wv[:, 0] > 0][:, 2:4].astype(np.float64) / ck[ok, 2][0]
+                    print(f"{'':12s} cycles a key per chain wave: median {np.median(w2):.2f}, min {w2.min():.2f}, max {w2.max():.2f}; "
+                          f"producer 0 polls a workgroup: median {np.median(ch[:, 7]):.0f}")
         elif k == 1:
             kv, rdy, cnt = x[:, 1], x[:, 2], x[:, 3]
             lastb = x[x[:, 4] > 0]
