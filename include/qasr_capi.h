@@ -720,6 +720,77 @@ typedef struct {
 } qasr_kt_sample_args;
 int qasr_kt_sample(int device, qasr_kt_sample_args *a);
 
+/* ---- decoding constraints ---------------------------------- */
+/* With constraints on, the fp32 logits of every prefill and decode step are edited on the device before a
+ * token is chosen, and the token is chosen again from the edited row (the rule is normative, DESIGN.md §5.6
+ * and tests/constrain_util.py; every operation is one rounded fp32 operation, so it is exact).  For a row
+ * with raw logits l and history h[0 .. t) (the tokens the engine returned for that row since its last
+ * prefill, the prefill's own token included), in this order:
+ *   1. repetition_penalty p != 1: every distinct token v among the last penalty_last_n tokens of h (0: all
+ *      of h) gets l[v] > 0 ? l[v] * (1 / p) : l[v] * p;
+ *   2. every listed token gets l[bias_ids[k]] += bias[k] (-inf suppresses the token);
+ *   3. no_repeat_ngram n >= 1: every token that would complete an n-gram h already holds gets -inf (n = 1
+ *      bans every token seen);
+ *   4. the token is the largest value of the edited row, equal values by lower id.
+ * The edited row replaces the step's logits everywhere: the `logits` output of qasr_prefill* and
+ * qasr_decode_step, option token_logprobs (log softmax of the edited row), option top_k (entry 0 is the
+ * constrained token) and the sampler (qasr_set_sampling draws from the edited row).
+ * Covered: qasr_prefill*, qasr_decode_step, qasr_run, qasr_run_staged, qasr_transcribe_batch, with sampling at
+ * any n_best, f16 and Q8_0 models.  At stage level the history is the engine's own record of what its calls
+ * returned: qasr_decode_step continues the history of the last prefill whatever tokens the caller feeds back
+ * (QASR_ERR_STATE once it holds max_ctx tokens).  While constraints are on, qasr_run_stream* and option
+ * beam_width >= 2 are refused with QASR_ERR_STATE; qasr_score / qasr_prefill_score are unaffected; aligner
+ * models ignore the setting.  Changing the values re-captures no step graph; with constraints off nothing of
+ * the other paths changes. */
+#define QASR_NGRAM_MAX 8
+#define QASR_BIAS_MAX 1024
+typedef struct {
+    int32_t no_repeat_ngram;      /* 0 = off, 1 .. QASR_NGRAM_MAX */
+    float repetition_penalty;     /* 0 < p <= 10, 1 = off */
+    int32_t penalty_last_n;       /* >= 0, 0 = the whole history */
+    int32_t n_bias;               /* 0 .. QASR_BIAS_MAX */
+    const int32_t *bias_ids;      /* [n_bias] distinct ids in [0, vocab) */
+    const float *bias;            /* [n_bias] each finite or -inf */
+} qasr_constraints;
+/* Host only (no device): 0, or QASR_ERR_ARG with a message naming the violated range.  vocab <= 0: the ids'
+ * upper bound is not checked. */
+int qasr_constraints_validate(const qasr_constraints *k, int vocab);
+/* NULL, or no_repeat_ngram = 0, repetition_penalty = 1 and n_bias = 0 together, turns constraints off; any
+ * n_bias > 0 turns them on.  QASR_ERR_ARG as qasr_constraints_validate; QASR_ERR_STATE for a model whose
+ * vocabulary exceeds 2^20. */
+int qasr_set_constraints(qasr_ctx *c, const qasr_constraints *k);
+/* The setting in force (n_bias = 0 and the neutral values while off).  ids / bias [cap] receive the bias list
+ * where they are non-NULL (cap < n_bias: QASR_ERR_ARG); out's two pointers are set to ids / bias. */
+int qasr_get_constraints(const qasr_ctx *c, qasr_constraints *out, int32_t *ids, float *bias, int cap);
+
+/* test only: launch_constrain (csrc/constrain.hip) on caller-supplied arrays, `launches` (>= 1) times, each from
+ * the same device state (the logits are uploaded again before every launch).  In: logits [R / src_div][ld],
+ * greedy [R / src_div] (each inside [0, n_valid)), hist [R][hist_stride] (ids inside [0, n_valid)), t (0 ..
+ * hist_stride - 1: the history length and the slot written) and the parameters.  Out: tok [R + 2 guard] and
+ * hist_slot [R + 2 guard] (the history slot t of every row; the rest of the history must come back unchanged,
+ * which the call checks) with the guard entries 0xFF before the launch; logits_out [R / src_div + 2 guard][ld],
+ * the edited rows between guard rows of 0xFF; skey_out / flag_out [R / src_div]: the scratch after the last
+ * launch (zero at rest; each lies between two 4 KiB fences of 0xFF the launch must leave alone).  slices: 0 =
+ * the launcher's choice. */
+typedef struct {
+    int32_t R, ld, n_valid, src_div, slices, guard, launches, hist_stride, t;
+    int32_t no_repeat_ngram;
+    float repetition_penalty;
+    int32_t penalty_last_n, n_bias;
+    const int32_t *bias_ids;
+    const float *bias;
+    const float *logits;
+    const int32_t *greedy, *hist;
+    int32_t *tok, *hist_slot;
+    float *logits_out;
+    uint64_t *skey_out;
+    int32_t *flag_out;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_constrain_args;
+int qasr_kt_constrain(int device, qasr_kt_constrain_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "audio_encoder.h"
@@ -46,6 +47,16 @@ struct transcribe_params {
     float min_p = 0.f;
     uint64_t seed = 0;
     int32_t n_best = 1;
+    // MI355X addition (trailing, default off): decoding constraints (qasr_set_constraints of qasr_capi.h; no reference
+    // counterpart), applied to every step's logits before a token is chosen.  no_repeat_ngram n (1..8): no n-gram of
+    // tokens occurs twice; repetition_penalty p (0 < p <= 10, 1 = off) over the last penalty_last_n tokens (0 = all);
+    // suppress_tokens are never emitted; token_bias adds to the listed tokens' logits (at most 1024 tokens in both
+    // lists together, a token in both is suppressed).  Excludes beam_width >= 2 and transcribe_stream
+    int32_t no_repeat_ngram = 0;
+    float repetition_penalty = 1.f;
+    int32_t penalty_last_n = 0;
+    std::vector<int32_t> suppress_tokens;
+    std::vector<std::pair<int32_t, float>> token_bias;
 };
 
 // MI355X addition: one hypothesis of a beam run
@@ -160,6 +171,7 @@ private:
     bool set_top_k(int k);
     bool set_beam_width(int w);
     bool set_sampling(const transcribe_params &params);
+    bool set_constraints(const transcribe_params &params);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

@@ -61,8 +61,12 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     // (a beam run: K = its width, whatever option top_k says)
     const int K = step_k(c);
     const bool tk = K > 0;
-    const bool tk_fused = tk && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && K <= kLmhTopkAutoMax));
+    // decoding constraints: the stage edits the fp32 logits after the bookkeeping and chooses again; the log-probability
+    // and the alternatives are the edited row's, so neither comes from the one-launch heads' fused groups (the raw row's)
+    const bool con = constraints_on(c);
+    const bool tk_fused = tk && !con && lmh_one && B <= 64 && (c->fuse.lmh_topk >= 2 || (c->fuse.lmh_topk == 1 && K <= kLmhTopkAutoMax));
     if (tk && !tk_fused) want_logits = true;
+    if (con) want_logits = true;
     // sampling: the draw reads the fp32 logits after the bookkeeping, and the drawn token's log-probability comes from
     // them too (the fused LSE's value would be the argmax's)
     const bool smp = sampling_on(c);
@@ -235,18 +239,23 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
             lm.stamp = stamp;
             if (skinny) {   // amax / done are zero at rest: the LM head's last workgroup re-arms them
                 launch_gemv(EPI_ARGMAX, lm, s);
+                if (con && (rc = constrain_step(c, B, 1))) return rc;
                 if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
                 if (tk && (rc = topk_step(c, B))) return rc;
             } else {   // norm + GEMM + argmax + bookkeeping in one launch (lmhead.hip)
                 lm.nkv = c->d_nkv;
                 // (the top-K variant carries the log-sum-exp code: d_lp / d_lphist are written with either option)
-                if ((lp && !smp) || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
+                if ((lp && !smp && !con) || tk_fused) { lm.lp_part = c->d_lppart; lm.lp_out = c->d_lp; lm.lp_hist = c->d_lphist; }
                 if (tk_fused) {
                     lm.tk_part = c->d_tkpart; lm.tk_out = c->d_tkid; lm.tk_lp = c->d_tklp; lm.tk_hist = c->d_tkhid;
                     lm.tk_lphist = c->d_tkhlp; lm.tk_k = K;
                 }
                 if (!launch_lmhead_batch(lm, s))   // (lmh_one mirrors its shape conditions: never expected)
                     return fail(QASR_ERR_STATE, "decode step: the batched LM head declined B = " + std::to_string(B));
+                if (con) {
+                    if ((rc = constrain_step(c, B, 1))) return rc;
+                    if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
+                }
                 if (tk && !tk_fused && (rc = topk_step(c, B))) return rc;
             }
         } else {
@@ -261,6 +270,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     if (r.in(2 + 2 * nl) && !skinny && !lmh_one) {   // bookkeeping (fused into the LM-head GEMV at batch <= 8)
         launch_step_advance(c->d_pos, c->d_nkv, c->d_step, B, s);
         launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
+        if (con && (rc = constrain_step(c, B, 1))) return rc;
         if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
         if (tk && (rc = topk_step(c, B))) return rc;
         launch_fill_u64(c->d_amax, B, 0ull, s);   // re-arm (zero at rest)
@@ -489,7 +499,12 @@ extern "C" int qasr_decode_step(qasr_ctx *c, const int32_t *tok, const int *n_pa
     HIPCHK(hipMemcpyAsync(c->d_tok, tok, B * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->d_pos, pos.data(), B * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->d_nkv, nkv.data(), B * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemsetAsync(c->d_step, 0, 4, c->st));
+    // constraints on: the rows' history goes on from the last prefill (the step writes slot stage_t + 1); else slot 1 of a
+    // history nothing reads
+    const bool con = constraints_on(c);
+    if (con && c->stage_t + 2 > c->hist_cap) return fail(QASR_ERR_STATE, "constraints: the history holds max_ctx tokens (prefill again)");
+    if (con) HIPCHK(hipMemcpyAsync(c->d_step, &c->stage_t, 4, hipMemcpyHostToDevice, c->st));
+    else HIPCHK(hipMemsetAsync(c->d_step, 0, 4, c->st));
     if (int rc = decode_step_kernels(c, B, logits != nullptr, kWholeStep, split_bucket(c, *std::max_element(pos.begin(), pos.end()))))
         return rc;
     HIPCHK(hipGetLastError());
@@ -498,6 +513,7 @@ extern "C" int qasr_decode_step(qasr_ctx *c, const int32_t *tok, const int *n_pa
     HIPCHK(hipStreamSynchronize(c->st));
     c->lp_step_B = c->fuse.token_logprobs ? B : 0;
     c->tk_step_B = c->fuse.top_k ? B : 0;
+    if (con) c->stage_t++;
     return check_dev_err(c);
 }
 

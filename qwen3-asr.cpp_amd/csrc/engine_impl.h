@@ -8,6 +8,7 @@
 //   engine_run.hip     qasr_run, the continuous-batching stream, their log-probability readers
 //   engine_beam.hip    beam search: the KV-cache fork entry, the beam loop, the hypothesis reader
 //   engine_sample.hip  temperature sampling: qasr_set_sampling, the sampler step, the n_best run, the sample reader
+//   engine_constrain.hip  decoding constraints: qasr_set_constraints, the constraint stage of a prefill or decode step
 //   engine_score.hip   teacher-forced scoring: the score head over prefill rows, qasr_prefill_score, qasr_score
 //   engine_align.hip   the forced aligner and its JSON output
 #pragma once
@@ -206,6 +207,26 @@ struct qasr_ctx {
     int last_run_nbest = 0;            // ... with this n_best
     struct SampleHyp { std::vector<int32_t> tokens; std::vector<float> logprobs; float sum = 0.f; };
     std::vector<std::vector<SampleHyp>> samp_res;   // its hypotheses per clip, in sample order
+    // decoding constraints (engine_constrain.hip): off until qasr_set_constraints turns them on.  The
+    // device state is allocated the first time (ensure_constrain): the parameters and the bias list a captured step
+    // reads, per logits row the key the scan folds into and its flag (both zero at rest) and the constrained token
+    struct ConstrainState {
+        bool on = false;
+        int ngram = 0;
+        float p = 1.f;
+        int last_n = 0;
+        std::vector<int32_t> ids;
+        std::vector<float> bias;
+    } con;
+    struct ConstrainDev {
+        qasr::ConstrainParams *prm = nullptr;
+        int32_t *ids = nullptr;
+        float *bias = nullptr;
+        unsigned long long *skey = nullptr;
+        int *flag = nullptr;
+        int32_t *gtok = nullptr;
+    } cd;
+    int stage_t = 0;                   // constraints on: the history length of the rows of qasr_prefill* / qasr_decode_step
     long n_captures = 0;               // step graphs captured so far (option "graph_captures", read-only)
     DevBuf fork_args;                  // qasr_kv_fork: the caller's parent | from | to on the device
     // teacher-forced scoring (engine_score.hip): the gathered normed rows (fp16), row indices | targets, the three
@@ -309,7 +330,12 @@ int ensure_beam(qasr_ctx *c);
 // graph key's first entry (a beam run's width, or 16 x the rows per clip of a sampling step)
 inline bool sampling_on(const qasr_ctx *c) { return c->samp.temperature > 0.f && !c->m->hp.aligner; }
 inline int sample_mul(const qasr_ctx *c) { return std::max(1, c->samp_run_N); }
-inline int step_mode(const qasr_ctx *c) { return c->beam_W >= 2 ? c->beam_W : sampling_on(c) ? 16 * sample_mul(c) : 0; }
+// decoding constraints: on for this context's decoding (aligner models ignore them)
+inline bool constraints_on(const qasr_ctx *c) { return c->con.on && !c->m->hp.aligner; }
+// (constraints on: 1024 on top, a key of its own beside every other mode's)
+inline int step_mode(const qasr_ctx *c) {
+    return (c->beam_W >= 2 ? c->beam_W : sampling_on(c) ? 16 * sample_mul(c) : 0) + (constraints_on(c) ? 1024 : 0);
+}
 int dev_alloc(qasr_ctx *c, void **p, size_t bytes);
 
 // V^T cache elements of one layer
@@ -381,6 +407,11 @@ int sample_set_streams(qasr_ctx *c, const std::vector<int> &clip, const std::vec
 int sample_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
 // the hypotheses of a sampling run from its token history (rows g * N + i) and d_lphist -> c->samp_res
 int sample_collect(qasr_ctx *c, int G, int N, const std::vector<int32_t> &hist, int steps, int max_tokens, int ignore_eos);
+
+// engine_constrain.hip
+// the constraint stage after the bookkeeping of a prefill or decode step: B token rows, row r from logits row
+// r / src_div; d_logits becomes the edited rows, d_tok and the history slot the constrained tokens
+int constrain_step(qasr_ctx *c, int B, int src_div);
 
 // engine_run.hip
 int greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::vector<int32_t> &hist, int &steps);

@@ -259,6 +259,8 @@ extern "C" int qasr_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *to
     if (!c || max_tokens <= 0 || !tokens || !n_tokens) return fail(QASR_ERR_ARG, "bad arguments");
     const int B = (int)c->staged_n.size();
     if (B == 0) return fail(QASR_ERR_STATE, "no staged audio");
+    if (constraints_on(c) && c->fuse.beam_width >= 2)
+        return fail(QASR_ERR_STATE, "decoding constraints and beam search (option beam_width >= 2) exclude each other");
     if (sampling_on(c)) return sample_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
     c->last_run_sampled = false;
     if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return beam_run(c, max_tokens, ignore_eos, tokens, n_tokens, t);
@@ -344,6 +346,7 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
     if (!c || !sink || max_tokens <= 0 || slots < 0 || slots > c->max_batch) return fail(QASR_ERR_ARG, "bad arguments");
     if (c->fuse.beam_width >= 2 && !c->m->hp.aligner) return fail(QASR_ERR_STATE, "the continuous-batching stream has no beam search (option beam_width >= 2)");
     if (sampling_on(c)) return fail(QASR_ERR_STATE, "the continuous-batching stream has no sampling (qasr_set_sampling)");
+    if (constraints_on(c)) return fail(QASR_ERR_STATE, "the continuous-batching stream has no decoding constraints (qasr_set_constraints)");
     HIPCHK(hipSetDevice(c->m->device));
     const int S = slots ? slots : c->max_batch;
     std::unique_lock<std::mutex> dev_lk;

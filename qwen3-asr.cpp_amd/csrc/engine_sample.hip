@@ -89,7 +89,8 @@ int qasr::eng::sample_step(qasr_ctx *c, int B, int src_div) {
     if (B > c->max_batch) return fail(QASR_ERR_ARG, "sampling: rows exceed the context's max_batch");
     SampleArgs a{};
     a.logits = c->d_logits; a.ld = V; a.n_valid = V;
-    a.greedy = c->d_tok;
+    // (constraints on: the draw is from the edited rows, whose maxima are the constraint stage's tokens per logits row)
+    a.greedy = constraints_on(c) ? c->cd.gtok : c->d_tok;
     a.clip = c->sd.clip; a.sample = c->sd.sample; a.t = c->sd.t;
     a.sc = c->sd.sc; a.skey = c->sd.skey;
     a.tok = c->d_tok; a.hist = c->d_hist; a.hist_stride = c->hist_cap; a.step = c->d_step;

@@ -404,7 +404,8 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     launch_fill_u64(c->d_amax, B, 0ull, s);
     const bool lp = c->fuse.token_logprobs != 0;   // the log-probabilities come from the fp32 logits
     const bool smp = sampling_on(c);   // sampling: the draw and its log-probability read them too
-    want_logits = want_logits || lp || step_k(c) > 0 || smp;   // (option top_k or a beam run: the alternatives likewise)
+    const bool con = constraints_on(c);   // decoding constraints: the stage edits them and chooses again
+    want_logits = want_logits || lp || step_k(c) > 0 || smp || con;   // (option top_k or a beam run: the alternatives likewise)
     if (B <= 8) {
         GemvArgs gv{};
         gv.xh = xl; gv.ldxh = H; gv.W = m->embd; gv.K = H; gv.N = hp.vocab; gv.M = B;
@@ -418,6 +419,9 @@ int qasr::eng::run_prefill(qasr_ctx *c, const std::vector<int32_t> &ids, const s
     }
     HIPCHK(hipMemsetAsync(c->d_step, 0, 4, s));
     launch_argmax_finish(c->d_amax, B, c->d_tok, c->d_hist, c->hist_cap, c->d_step, s);
+    // constraints: token 0 from the edited rows (an empty history: the bias list alone can act), before anything reads them
+    c->stage_t = 0;
+    if (con && (rc = constrain_step(c, B * sample_mul(c), sample_mul(c)))) return rc;
     if (lp && !smp) launch_token_logprob(c->d_logits, hp.vocab, B, 0, c->d_tok, c->d_step, c->d_lp, c->d_lphist, c->hist_cap, s);
     if ((rc = topk_step(c, B))) return rc;
     launch_fill_u64(c->d_amax, B, 0ull, s);   // zero at rest for the decode graph

@@ -414,3 +414,67 @@ extern "C" int qasr_kt_sample(int device, qasr_kt_sample_args *a) {
         return rc;
     return 0;
 }
+
+// ------------------------------------------------------- decoding constraints
+extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) {
+    if (!a) return fail(QASR_ERR_ARG, "bad arguments");
+    if (a->R <= 0 || a->ld <= 0 || a->n_valid <= 0 || a->n_valid > a->ld || a->src_div < 1 || a->R % a->src_div != 0 || a->slices < 0 ||
+        a->guard < 0 || a->launches < 1 || a->hist_stride < 1 || a->t < 0 || a->t >= a->hist_stride || !a->logits || !a->greedy || !a->hist ||
+        !a->tok || !a->hist_slot || !a->logits_out || !a->skey_out || !a->flag_out)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const qasr_constraints k{a->no_repeat_ngram, a->repetition_penalty, a->penalty_last_n, a->n_bias, a->bias_ids, a->bias};
+    int rc;
+    if ((rc = qasr_constraints_validate(&k, a->n_valid))) return rc;
+    const int R = a->R, RS = R / a->src_div, G = a->guard, HS = a->hist_stride;
+    for (int r = 0; r < RS; r++)
+        if (a->greedy[r] < 0 || a->greedy[r] >= a->n_valid) return fail(QASR_ERR_ARG, "greedy id outside [0, n_valid)");
+    for (size_t i = 0; i < (size_t)R * HS; i++)
+        if (a->hist[i] < 0 || a->hist[i] >= a->n_valid) return fail(QASR_ERR_ARG, "history id outside [0, n_valid)");
+    if ((rc = use_device(device))) return rc;
+    KtBuf lg, gr, hs, prm, ids, bias, step, tok;
+    KtFenced skey, flag;
+    const ConstrainParams cp{a->no_repeat_ngram, a->repetition_penalty, 1.0f / a->repetition_penalty, a->penalty_last_n, a->n_bias};
+    std::vector<int32_t> idv(QASR_BIAS_MAX, 0);
+    std::vector<float> bv(QASR_BIAS_MAX, 0.f);
+    std::copy(a->bias_ids, a->bias_ids + a->n_bias, idv.begin());
+    std::copy(a->bias, a->bias + a->n_bias, bv.begin());
+    const std::vector<unsigned long long> rest(RS, 0ull);
+    const std::vector<int> rest_flag(RS, 0);
+    const size_t row_bytes = (size_t)a->ld * 4, hist_bytes = (size_t)R * HS * 4;
+    if ((rc = put_out(lg, a->logits_out, RS, a->ld, 4, G)) || (rc = put_state(gr, a->greedy, (size_t)RS * 4)) ||
+        (rc = put_out(hs, a->hist, R, HS, 4, G)) || (rc = put_state(prm, &cp, sizeof cp)) ||
+        (rc = put_state(ids, idv.data(), idv.size() * 4)) || (rc = put_state(bias, bv.data(), bv.size() * 4)) ||
+        (rc = put_state(step, &a->t, 4)) || (rc = put_out(tok, a->tok, R, 1, 4, G)) || (rc = skey.put(rest.data(), (size_t)RS * 8)) ||
+        (rc = flag.put(rest_flag.data(), (size_t)RS * 4)))
+        return rc;
+    ConstrainArgs s{};
+    s.logits = lg.ptr<float>(); s.ld = a->ld; s.n_valid = a->n_valid;
+    s.greedy = gr.ptr<int32_t>();
+    s.hist_in = hs.ptr<int32_t>(); s.hist_stride = HS; s.step = step.ptr<int>();
+    s.prm = prm.ptr<ConstrainParams>(); s.bias_ids = ids.ptr<int32_t>(); s.bias = bias.ptr<float>();
+    s.skey = skey.b.ptr<unsigned long long>(); s.flag = flag.b.ptr<int>();
+    s.tok = tok.ptr<int32_t>(); s.hist = hs.ptr<int32_t>();
+    s.R = R; s.src_div = a->src_div;
+    bool ran = true;
+    for (int i = 0; i < a->launches && ran; i++) {   // (the same device state before every launch)
+        HIPCHK(hipMemcpy(lg.ptr<char>(), a->logits, (size_t)RS * row_bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(hs.ptr<char>(), a->hist, hist_bytes, hipMemcpyHostToDevice));
+        ran = launch_constrain(s, a->slices, nullptr);
+        if (ran && i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
+    }
+    if ((rc = finish(a, ran))) return rc;
+    // the history: slot t of every row out; every other entry and the guard rows as they were
+    std::vector<int32_t> hall(hs.bytes / 4);
+    if ((rc = get(hs, hall.data()))) return rc;
+    for (int i = 0; i < R + 2 * G; i++) a->hist_slot[i] = -1;
+    for (size_t i = 0; i < hall.size(); i++) {
+        const long row = (long)(i / HS) - G, col = (long)(i % HS);
+        const bool real = row >= 0 && row < R;
+        if (real && col == a->t) a->hist_slot[G + row] = hall[i];
+        else if (hall[i] != (real ? a->hist[(size_t)row * HS + col] : -1)) return fail(QASR_ERR_STATE, "a write outside the history slot");
+    }
+    if ((rc = get(tok, a->tok)) || (rc = get(lg, a->logits_out)) || (rc = skey.take(a->skey_out, "the key scratch")) ||
+        (rc = flag.take(a->flag_out, "the flag scratch")))
+        return rc;
+    return 0;
+}

@@ -521,4 +521,35 @@ bool launch_sample(const SampleArgs &a, int slices, hipStream_t s);   // false =
 // test only: out[i] = G(u_n) of the rule's step 2 and 3 for n = n0 + i
 void launch_sample_gumbel_dump(uint32_t n0, uint32_t n, float *out, hipStream_t s);
 
+// ---------------------------------------------------------------- decoding constraints (constrain.hip)
+// Sparse edits of a step's fp32 logits row, then a new greedy choice (the normative rule): the
+// repetition penalty on the distinct tokens of the history window, the additive bias list, the no-repeat n-gram
+// ban, in that order; the token is the largest argmax_key of the edited row.  Logits row q serves token rows
+// q * src_div .. q * src_div + src_div - 1 (src_div = n_best at a hypothesis' first step, else 1) and is edited
+// once, by the history of its first token row.  The parameters and the bias list are device memory, so a captured
+// step serves any of their values.
+constexpr int kConstrainNgramMax = 8, kConstrainBiasMax = 1024, kConstrainVocabMax = 1 << 20;
+struct ConstrainParams {
+    int ngram;                           // 0 = off, else 1 .. kConstrainNgramMax
+    float p, inv_p;                      // the penalty and 1.0f / p, rounded on the host (p == 1: off)
+    int last_n;                          // the penalty's window (0: the whole history)
+    int n_bias;                          // entries of bias_ids / bias in use
+};
+struct ConstrainArgs {
+    float *logits; int ld, n_valid;      // [R / src_div][ld], edited in place
+    const int32_t *greedy;               // [R / src_div] each raw row's argmax (d_tok before the stage)
+    const int32_t *hist_in; int hist_stride; const int *step;   // hist_in[r][0 .. *step): row r's history
+    const ConstrainParams *prm;          // [1]
+    const int32_t *bias_ids; const float *bias;   // [kConstrainBiasMax]
+    unsigned long long *skey;            // [R / src_div] zero at rest, re-armed by the launch
+    int *flag;                           // [R / src_div] the row takes the scan (its greedy column was edited); zero at rest
+    int32_t *tok;                        // [R] out: the constrained tokens (may alias greedy)
+    int32_t *hist;                       // hist[r][*step] = tok[r] (may alias hist_in; null: not written)
+    int32_t *gtok;                       // [R / src_div] out: the token per logits row (null: not written)
+    int R, src_div;
+};
+// slices a row's scan is spread over where the caller passes 0
+int constrain_slices(int R, int n_valid);
+bool launch_constrain(const ConstrainArgs &a, int slices, hipStream_t s);   // false = bad shape, nothing launched
+
 }  // namespace qasr

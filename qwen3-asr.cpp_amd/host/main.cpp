@@ -9,6 +9,8 @@
 #include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <climits>
+#include <cmath>
 #include <chrono>
 #include <sys/stat.h>
 #include <mutex>
@@ -39,6 +41,11 @@ struct cli_params {
     float temperature = 0.f, min_p = 0.f;   // --temperature / --min-p / --seed / --n-best: sampling (transcribe_params)
     uint64_t seed = 0;
     int32_t n_best = 1;
+    // --no-repeat-ngram / --repetition-penalty / --penalty-last-n / --suppress-tokens / --token-bias: decoding constraints
+    int32_t no_repeat_ngram = 0, penalty_last_n = 0;
+    float repetition_penalty = 1.f;
+    std::vector<int32_t> suppress_tokens;
+    std::vector<std::pair<int32_t, float>> token_bias;
     std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
 };
@@ -63,6 +70,11 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --seed <n>             With --temperature: the 64-bit seed of the draws (default: 0)\n");
     fprintf(stderr, "  --n-best <n>           With --temperature: n (1..8) samples a file; n > 1 lists every sample with its\n");
     fprintf(stderr, "                         summed log-probability (the output is sample 0's text)\n");
+    fprintf(stderr, "  --no-repeat-ngram <n>  No n-gram (1..8) of tokens occurs twice in a transcript (0: off)\n");
+    fprintf(stderr, "  --repetition-penalty <p>  Penalise tokens already emitted, 0 < p <= 10 (1: off)\n");
+    fprintf(stderr, "  --penalty-last-n <n>   With --repetition-penalty: only the last n tokens count (0: all)\n");
+    fprintf(stderr, "  --suppress-tokens <id,id,...>  Token ids never emitted\n");
+    fprintf(stderr, "  --token-bias <id:val,...>  Add val to the logit of token id before every choice\n");
     fprintf(stderr, "  --score <text>         Score <text> as a transcript of the -f file instead of transcribing (repeatable):\n");
     fprintf(stderr, "                         per text the summed log-probability, the mean per token and the token count\n");
     fprintf(stderr, "                         (the EOS included); with --tokens every token's id, text and log-probability,\n");
@@ -150,6 +162,44 @@ static bool parse(int argc, char **argv, cli_params &p) {
             if (!val(v)) return false;
             p.n_best = atoi(v.c_str());
             if (p.n_best < 1 || p.n_best > 8) { fprintf(stderr, "Error: --n-best takes 1..8\n"); return false; }
+        }
+        else if (!strcmp(a, "--no-repeat-ngram")) {
+            if (!val(v)) return false;
+            p.no_repeat_ngram = atoi(v.c_str());
+            if (p.no_repeat_ngram < 0 || p.no_repeat_ngram > 8) { fprintf(stderr, "Error: --no-repeat-ngram takes 0..8\n"); return false; }
+        }
+        else if (!strcmp(a, "--repetition-penalty")) {
+            if (!val(v)) return false;
+            p.repetition_penalty = (float)atof(v.c_str());
+            if (!(p.repetition_penalty > 0.f && p.repetition_penalty <= 10.f)) { fprintf(stderr, "Error: --repetition-penalty takes 0 < p <= 10\n"); return false; }
+        }
+        else if (!strcmp(a, "--penalty-last-n")) {
+            if (!val(v)) return false;
+            p.penalty_last_n = atoi(v.c_str());
+            if (p.penalty_last_n < 0) { fprintf(stderr, "Error: --penalty-last-n takes 0 or more\n"); return false; }
+        }
+        else if (!strcmp(a, "--suppress-tokens") || !strcmp(a, "--token-bias")) {
+            const bool sup = a[2] == 's';
+            if (!val(v)) return false;
+            size_t at = 0;
+            while (at <= v.size()) {   // id[,id...] or id:val[,id:val...]
+                const size_t end = std::min(v.find(',', at), v.size());
+                const std::string item = v.substr(at, end - at);
+                char *rest = nullptr;
+                const long id = strtol(item.c_str(), &rest, 10);
+                bool ok = !item.empty() && rest != item.c_str() && id >= 0 && id <= INT32_MAX;
+                float b = 0.f;
+                if (ok && sup) ok = *rest == 0;
+                if (ok && !sup) {
+                    char *tail = nullptr;
+                    ok = *rest == ':' && rest[1] != 0;
+                    if (ok) { b = strtof(rest + 1, &tail); ok = *tail == 0 && (std::isfinite(b) || b == -INFINITY); }
+                }
+                if (!ok) { fprintf(stderr, sup ? "Error: --suppress-tokens takes id,id,...\n" : "Error: --token-bias takes id:val,...\n"); return false; }
+                if (sup) p.suppress_tokens.push_back((int32_t)id);
+                else p.token_bias.push_back({(int32_t)id, b});
+                at = end + 1;
+            }
         }
         else if (!strcmp(a, "--score")) { if (!val(v)) return false; p.score_texts.push_back(v); }
         else if (!strcmp(a, "--profile")) p.profile = true;
@@ -462,6 +512,11 @@ static int run_transcription(const cli_params &p) {
     tp.min_p = p.min_p;
     tp.seed = p.seed;
     tp.n_best = p.n_best;
+    tp.no_repeat_ngram = p.no_repeat_ngram;
+    tp.repetition_penalty = p.repetition_penalty;
+    tp.penalty_last_n = p.penalty_last_n;
+    tp.suppress_tokens = p.suppress_tokens;
+    tp.token_bias = p.token_bias;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));

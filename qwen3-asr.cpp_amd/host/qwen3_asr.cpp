@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 
 #include "qasr_host.h"
@@ -143,6 +144,30 @@ bool Qwen3ASR::set_sampling(const transcribe_params &params) {
     return true;
 }
 
+// decoding constraints as the call asks (qasr_set_constraints: no graph is dropped either way)
+static bool constraints_asked(const transcribe_params &params) {
+    return params.no_repeat_ngram != 0 || params.repetition_penalty != 1.f || !params.suppress_tokens.empty() || !params.token_bias.empty();
+}
+
+bool Qwen3ASR::set_constraints(const transcribe_params &params) {
+    std::vector<int32_t> ids;
+    std::vector<float> bias;
+    auto put = [&](int32_t id, float b) {
+        for (size_t i = 0; i < ids.size(); i++)
+            if (ids[i] == id) { bias[i] = b; return; }
+        ids.push_back(id);
+        bias.push_back(b);
+    };
+    for (const auto &tb : params.token_bias) put(tb.first, tb.second);
+    for (const int32_t id : params.suppress_tokens) put(id, -INFINITY);
+    qasr_constraints k{params.no_repeat_ngram, params.repetition_penalty, params.penalty_last_n, (int32_t)ids.size(), ids.data(), bias.data()};
+    if (qasr_set_constraints(ctx_, constraints_asked(params) ? &k : nullptr) != 0) {
+        error_msg_ = std::string("Failed to set decoding constraints: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
 transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const transcribe_params &params) {
     transcribe_result result;
     if (!model_) { result.error_msg = "Model not loaded"; return result; }
@@ -195,7 +220,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     const int NB = sampling ? std::max(params.n_best, 1) : 1;
     const bool many = sampling && NB >= 2;
     if (!ensure_ctx(B * std::max(W, NB), maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
-        !set_top_k(params.top_k) || !set_beam_width(params.beam_width) || !set_sampling(params)) {
+        !set_top_k(params.top_k) || !set_beam_width(params.beam_width) || !set_sampling(params) || !set_constraints(params)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -310,7 +335,8 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
 std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std::vector<float>> &clips,
                                                           const transcribe_params &params) {
     if (clips.size() <= 1) return transcribe_run(clips, params);
-    if (params.beam_width >= 2 || params.temperature > 0.f) {   // the stream has neither beam search nor sampling: whole runs of as many clips as max_batch() rows hold
+    // the stream has neither beam search, sampling nor decoding constraints: whole runs of as many clips as max_batch() rows hold
+    if (params.beam_width >= 2 || params.temperature > 0.f || constraints_asked(params)) {
         std::vector<transcribe_result> out;
         const size_t per = (size_t)std::max(1, max_batch_ / std::max(1, params.beam_width >= 2 ? params.beam_width : params.n_best));
         for (size_t i = 0; i < clips.size(); i += per) {
@@ -406,8 +432,9 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
     if (params.beam_width >= 2) { error_msg_ = "The stream has no beam search (transcribe_params::beam_width)"; return false; }
     if (params.temperature > 0.f) { error_msg_ = "The stream has no sampling (transcribe_params::temperature)"; return false; }
+    if (constraints_asked(params)) { error_msg_ = "The stream has no decoding constraints (transcribe_params::no_repeat_ngram ...)"; return false; }
     if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) || !set_beam_width(0) ||
-        !set_sampling(params))
+        !set_sampling(params) || !set_constraints(params))
         return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream

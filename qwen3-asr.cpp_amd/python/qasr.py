@@ -39,6 +39,7 @@ EXPORTS = [
     "qasr_kv_fork", "qasr_get_beams", "qasr_prefill_slots",
     "qasr_prefill_score", "qasr_score",
     "qasr_set_sampling", "qasr_get_sampling", "qasr_set_sample_streams", "qasr_get_samples",
+    "qasr_constraints_validate", "qasr_set_constraints", "qasr_get_constraints",
 ]
 
 
@@ -68,8 +69,16 @@ class Sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64), ("n_best", C.c_int32)]
 
 
+class Constraints(C.Structure):
+    """qasr_constraints"""
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("repetition_penalty", C.c_float), ("penalty_last_n", C.c_int32),
+                ("n_bias", C.c_int32), ("bias_ids", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float))]
+
+
 QASR_BEAM_MAX = 8
 QASR_SAMPLE_MAX = 8
+QASR_NGRAM_MAX = 8
+QASR_BIAS_MAX = 1024
 _lib = None
 # void (*)(void *user, int seq, int n_generated, int32_t token)
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int32)
@@ -135,6 +144,9 @@ def lib() -> C.CDLL:
             "qasr_set_sampling": ([P, C.POINTER(Sampling)], I), "qasr_get_sampling": ([P, C.POINTER(Sampling)], I),
             "qasr_set_sample_streams": ([P, I32P, I32P, I32P, I], I),
             "qasr_get_samples": ([P, I, I32P, F, IP, F, I, I], I),
+            "qasr_constraints_validate": ([C.POINTER(Constraints), I], I),
+            "qasr_set_constraints": ([P, C.POINTER(Constraints)], I),
+            "qasr_get_constraints": ([P, C.POINTER(Constraints), I32P, F, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -163,6 +175,26 @@ def lib() -> C.CDLL:
 
 class QasrError(RuntimeError):
     pass
+
+
+def make_constraints(no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, penalty_last_n: int = 0, bias=None,
+                     suppress=None):
+    """a qasr_constraints from Python values, with the arrays it points into (keep them alive as long as it is
+    used); a token both biased and suppressed is suppressed"""
+    table = {int(i): float(b) for i, b in (bias or {}).items()}
+    for i in (suppress or ()):
+        table[int(i)] = float("-inf")
+    ids = np.array(list(table.keys()), np.int32)
+    val = np.array(list(table.values()), np.float32)
+    k = Constraints(int(no_repeat_ngram), float(repetition_penalty), int(penalty_last_n), len(ids),
+                    _i32(ids) if len(ids) else None, _f(val) if len(ids) else None)
+    return k, (ids, val)
+
+
+def constraints_validate(vocab: int = 0, **kw) -> None:
+    """qasr_constraints_validate (host only): raises QasrError naming the violated range"""
+    k, _keep = make_constraints(**kw)
+    _check(lib().qasr_constraints_validate(C.byref(k), int(vocab)), "qasr_constraints_validate")
 
 
 def _check(rc: int, what: str) -> None:
@@ -574,6 +606,22 @@ class Context:
         if n < 0:
             raise QasrError(f"qasr_get_samples: {lib().qasr_last_error().decode(errors='replace')}")
         return [Sample(toks[i, :nt[i]].tolist(), lps[i, :nt[i]].tolist(), float(sums[i])) for i in range(n)]
+
+    def set_constraints(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, penalty_last_n: int = 0,
+                        bias=None, suppress=None) -> None:
+        """qasr_set_constraints: bias {token id: additive bias}, suppress ids (a bias of -inf); the neutral values
+        with neither turn constraints off"""
+        k, _keep = make_constraints(no_repeat_ngram, repetition_penalty, penalty_last_n, bias, suppress)
+        _check(lib().qasr_set_constraints(self.h, C.byref(k)), "qasr_set_constraints")
+
+    def get_constraints(self) -> dict:
+        """qasr_get_constraints: the setting in force, the bias list as {token id: bias}"""
+        ids, bias = np.zeros(QASR_BIAS_MAX, np.int32), np.zeros(QASR_BIAS_MAX, np.float32)
+        k = Constraints()
+        _check(lib().qasr_get_constraints(self.h, C.byref(k), _i32(ids), _f(bias), QASR_BIAS_MAX), "qasr_get_constraints")
+        return {"no_repeat_ngram": int(k.no_repeat_ngram), "repetition_penalty": float(k.repetition_penalty),
+                "penalty_last_n": int(k.penalty_last_n),
+                "bias": {int(i): float(b) for i, b in zip(ids[:k.n_bias], bias[:k.n_bias])}}
 
     def _sampling_on(self) -> bool:
         return self.get_sampling().temperature > 0 and not self.model.is_aligner
