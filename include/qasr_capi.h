@@ -52,6 +52,10 @@
  *       no reference counterpart: teacher-forced scoring -- the log-probability
  *       of every token of a transcript the caller brings, from an LM head
  *       over many rows that never writes its logits
+ *   qasr_set_phrases, qasr_get_phrases, qasr_phrases_validate, qasr_phrase_tokenize
+ *       no reference counterpart: hotword boosting -- a list of token
+ *       sequences the decoder prefers, matched on the device against every
+ *       row's last tokens as one more edit of the constraint stage
  *
  * Conventions (mirroring the reference's):
  *   - return value: 0 = OK, nonzero = error; message via qasr_last_error().
@@ -790,6 +794,70 @@ typedef struct {
     char msg[256];
 } qasr_kt_constrain_args;
 int qasr_kt_constrain(int device, qasr_kt_constrain_args *a);
+
+/* ---- hotword boosting -------------------------------------- */
+/* A phrase list makes the decoder prefer given token sequences (hotwords, phrase hints, contextual biasing).
+ * It is one more edit of the constraint stage above, step 2b between the bias (2) and the ban (3), and the rule
+ * is as normative and as exact (tests/phrase_util.py).  For a row with history h[0 .. t): phrase
+ * k matches at position j (0 <= j < len_k) when j <= t and the row's last j tokens are the phrase's first j
+ * (j = 0 always matches); a match makes token ph_k[j] a candidate with bonus boost_k, and every token with a
+ * candidate gets l[x] += the largest of its candidates' bonuses: one rounded fp32 add a boosted column, after
+ * the bias and before the ban (a banned column stays -inf).  There is no cumulative score and nothing is taken
+ * back when a phrase is not completed.
+ * Phrases alone turn the constraint stage on; everything said above of the stage holds: the edited row is what
+ * the logits output, token_logprobs, top_k and the sampler read; qasr_run_stream* and beam_width >= 2 are
+ * refused with QASR_ERR_STATE while phrases are on; scoring is unaffected; aligner models ignore the setting.
+ * Changing the list, or turning phrases on or off while the stage stays on, re-captures no step graph. */
+#define QASR_PHRASE_MAX 4096
+#define QASR_PHRASE_LEN_MAX 16
+typedef struct {
+    int32_t n_phrases;     /* 0 .. QASR_PHRASE_MAX */
+    const int32_t *ids;    /* the phrases' tokens back to back, each in [0, vocab) */
+    const int32_t *len;    /* [n_phrases] each 1 .. QASR_PHRASE_LEN_MAX */
+    const float *boost;    /* [n_phrases] each finite, 0 < b <= 100 */
+} qasr_phrases;
+/* Host only (no device): 0, or QASR_ERR_ARG with a message naming the violated range.  vocab <= 0: the ids'
+ * upper bound is not checked.  Duplicates and phrases that are prefixes or suffixes of one another are allowed. */
+int qasr_phrases_validate(const qasr_phrases *p, int vocab);
+/* NULL or n_phrases = 0 turns phrases off.  QASR_ERR_ARG as qasr_phrases_validate, and for a list whose trie
+ * exceeds 65,536 edges (65,537 nodes); QASR_ERR_STATE for a model whose vocabulary exceeds 2^20. */
+int qasr_set_phrases(qasr_ctx *c, const qasr_phrases *p);
+/* The list in force (n_phrases = 0 while off).  ids [cap_ids], len / boost [cap_phrases] receive it where they
+ * are non-NULL (too small: QASR_ERR_ARG); out's pointers are set to them. */
+int qasr_get_phrases(const qasr_ctx *c, qasr_phrases *out, int32_t *ids, int32_t *len,
+                     float *boost, int cap_ids, int cap_phrases);
+/* host only: the tokenisations a hotword text needs -- of `text` (outer white space trimmed)
+ * and of " " + text, the second dropped when equal; returns their number (1 or 2), or minus
+ * an error code (empty text, a variant longer than 16 tokens, short buffers).  ids receives the variants back to
+ * back, len [2] their lengths. */
+int qasr_phrase_tokenize(const qasr_model *m, const char *text, int32_t *ids, int32_t *len,
+                         int cap_ids);
+
+/* test only: qasr_kt_constrain with a phrase list (compiled by csrc/phrase_host.h): the same arrays, guard rows,
+ * fences and re-armed scratch; scanned_out [R / src_div] receives per logits row whether it took the scan (its
+ * raw argmax was edited) or the fast path. */
+typedef struct {
+    int32_t R, ld, n_valid, src_div, slices, guard, launches, hist_stride, t;
+    int32_t no_repeat_ngram;
+    float repetition_penalty;
+    int32_t penalty_last_n, n_bias;
+    const int32_t *bias_ids;
+    const float *bias;
+    const float *logits;
+    const int32_t *greedy, *hist;
+    int32_t *tok, *hist_slot;
+    float *logits_out;
+    uint64_t *skey_out;
+    int32_t *flag_out;
+    int32_t n_phrases;
+    const int32_t *ph_ids, *ph_len;
+    const float *ph_boost;
+    int32_t *scanned_out;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_phrases_args;
+int qasr_kt_phrases(int device, qasr_kt_phrases_args *a);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,14 @@ struct transcribe_params {
     int32_t penalty_last_n = 0;
     std::vector<int32_t> suppress_tokens;
     std::vector<std::pair<int32_t, float>> token_bias;
+    // MI355X addition (trailing, default off): hotword boosting (qasr_set_phrases of qasr_capi.h; no reference
+    // counterpart).  Each hotword is tokenised with and without a leading space (qasr_phrase_tokenize, at most 16
+    // tokens a variant); while the last tokens spell the beginning of one, its next token's logit gets the boost
+    // (0 < boost <= 100).  hotword_boosts, where given, holds a boost per hotword (an entry <= 0, or a missing
+    // one: hotword_boost).  Excludes beam_width >= 2 and transcribe_stream
+    std::vector<std::string> hotwords;
+    float hotword_boost = 5.f;
+    std::vector<float> hotword_boosts;
 };
 
 // MI355X addition: one hypothesis of a beam run
@@ -172,6 +180,7 @@ private:
     bool set_beam_width(int w);
     bool set_sampling(const transcribe_params &params);
     bool set_constraints(const transcribe_params &params);
+    bool set_hotwords(const transcribe_params &params);
     std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
 
     qasr_model *model_ = nullptr;

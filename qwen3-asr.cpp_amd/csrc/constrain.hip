@@ -37,17 +37,87 @@ __device__ __forceinline__ unsigned long long block_key_max(unsigned long long b
     return best;
 }
 
+// ------------------------------------------------------------------ phrases
+// Step 2b for one row, called by every thread of its workgroup (barriers inside; the caller's edits of step 2 are
+// behind a barrier, and this returns behind one).  s_node[j] becomes the trie node h[t - j .. t) spells, or -1:
+// thread j walks from the root, each level a binary search in the node's ascending child tokens.  The nodes are
+// then taken deepest first, a barrier between depths: the thread whose atomicOr marks a child token in the
+// bitmap adds its bonus, a marked token is skipped -- so the deepest node that has the token decides, which with
+// the compiler's eff is the rule's maximum.  The children of one node are distinct: no two threads of a depth
+// touch one column.  Returns whether this thread boosted column g.
+__device__ __forceinline__ int phrase_boost(const PhraseTrie &ph, float *l, const int32_t *h, int t, int g, int n_valid,
+                                            uint32_t *s_seen, int *s_node) {
+    const int tid = threadIdx.x;
+    int *s_h = s_node + kPhraseWalkMax + 1;   // the last 15 tokens, s_h[i] = h[t - m + i]
+    const int m = min(t, kPhraseWalkMax);
+    for (int i = tid; i < (n_valid + 31) >> 5; i += kEditThreads) s_seen[i] = 0u;   // (the penalty's marks are spent)
+    if (tid < m) s_h[tid] = h[t - m + tid];
+    __syncthreads();
+    if (tid <= kPhraseWalkMax) {
+        int u = tid <= m ? 0 : -1;
+        for (int i = 0; i < tid && u >= 0; i++) {
+            const int x = s_h[m - tid + i];
+            int lo = ph.child_off[u];
+            const int end = ph.child_off[u + 1];
+            int hi = end;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ph.tok[mid] < x) lo = mid + 1; else hi = mid;
+            }
+            u = lo < end && ph.tok[lo] == x ? ph.dst[lo] : -1;
+            if ((unsigned)u >= (unsigned)ph.n_nodes) u = -1;   // (a header that does not fit its arrays: no walk out of them)
+        }
+        s_node[tid] = u;
+    }
+    __syncthreads();
+    int hit = 0;
+    for (int j = m; j >= 0; j--) {
+        const int u = s_node[j];
+        if (u >= 0) {
+            const int end = ph.child_off[u + 1];
+            for (int e = ph.child_off[u] + tid; e < end; e += kEditThreads) {
+                const int v = ph.tok[e];
+                if ((unsigned)v >= (unsigned)n_valid) continue;
+                const uint32_t bit = 1u << (v & 31);
+                if (!(atomicOr(&s_seen[v >> 5], bit) & bit)) {
+                    l[v] = l[v] + ph.bonus[e];
+                    hit |= v == g;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    return hit;
+}
+
+// the best key among the boosted columns as they stand (after the ban): the saved nodes' child lists again
+__device__ __forceinline__ unsigned long long phrase_keys(const PhraseTrie &ph, const float *l, int t, int n_valid, const int *s_node) {
+    unsigned long long best = 0ull;
+    for (int j = min(t, kPhraseWalkMax); j >= 0; j--) {
+        const int u = s_node[j];
+        if (u < 0) continue;
+        const int end = ph.child_off[u + 1];
+        for (int e = ph.child_off[u] + threadIdx.x; e < end; e += kEditThreads) {
+            const int v = ph.tok[e];
+            if ((unsigned)v < (unsigned)n_valid) best = key_max(best, argmax_key(l[v], v));
+        }
+    }
+    return best;
+}
+
 // ------------------------------------------------------------------ edit
 // LDS: one bit a column (dynamic, n_valid bits): the thread whose atomicOr sets a token's bit first is the
 // one that applies its penalty, so a token the window holds many times is penalised once, in O(window) work.
 __global__ __launch_bounds__(kEditThreads) void constrain_edit_kernel(ConstrainArgs a) {
     extern __shared__ uint32_t s_seen[];
     __shared__ unsigned long long s_best[kEditThreads / 64];
+    __shared__ int s_node[2 * (kPhraseWalkMax + 1)];   // the matched node per depth, then the last tokens
     const int q = blockIdx.x, tid = threadIdx.x;
     float *l = a.logits + (size_t)q * a.ld;
     const int32_t *h = a.hist_in + (size_t)q * a.src_div * a.hist_stride;
     const int gr = a.greedy[q], g = (unsigned)gr < (unsigned)a.n_valid ? gr : 0;   // (the row's argmax: always inside)
     const ConstrainParams prm = *a.prm;
+    const PhraseTrie ph = a.ph ? *a.ph : PhraseTrie{};   // (read with the parameters: no load waits behind the edits)
     const int t = min(max(*a.step, 0), a.hist_stride);
     const bool pen = prm.p != 1.0f;
     // the penalty's window h[lo .. t)
@@ -79,6 +149,8 @@ __global__ __launch_bounds__(kEditThreads) void constrain_edit_kernel(ConstrainA
         hit |= v == g;
     }
     __syncthreads();
+    // 2b. phrases: the nodes the row's last tokens spell, then one add a child token
+    if (ph.n_nodes > 0) hit |= phrase_boost(ph, l, h, t, g, a.n_valid, s_seen, s_node);
     // 3. ban: every token that followed an earlier occurrence of the last n - 1 tokens (the value is final:
     // its key is taken here)
     const int n = prm.ngram;
@@ -105,6 +177,7 @@ __global__ __launch_bounds__(kEditThreads) void constrain_edit_kernel(ConstrainA
         const int v = a.bias_ids[k];
         if ((unsigned)v < (unsigned)a.n_valid) best = key_max(best, argmax_key(l[v], v));
     }
+    if (ph.n_nodes > 0) best = key_max(best, phrase_keys(ph, l, t, a.n_valid, s_node));
     const int any_hit = __syncthreads_or(hit);
     best = block_key_max<kEditThreads>(best, s_best);
     if (tid == 0) {
@@ -149,6 +222,7 @@ __global__ __launch_bounds__(256) void constrain_finish_kernel(ConstrainArgs a) 
         if (a.hist) a.hist[(size_t)r * a.hist_stride + *a.step] = tok;
     }
     if (a.gtok) a.gtok[q] = tok;
+    if (a.scanned) a.scanned[q] = a.flag[q];
     a.skey[q] = 0ull;   // zero at rest
     a.flag[q] = 0;
 }

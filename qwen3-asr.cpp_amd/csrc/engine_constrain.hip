@@ -1,8 +1,10 @@
 // engine_constrain.hip -- decoding constraints: qasr_constraints_validate, qasr_set_constraints /
 // qasr_get_constraints and the constraint stage that follows the bookkeeping of a prefill or decode step while
 // constraints are on (constrain.hip: the edits of the fp32 logits, then the constrained token into d_tok and the
-// history slot the bookkeeping just wrote).
+// history slot the bookkeeping just wrote).  Hotword boosting is part of the same stage:
+// qasr_phrases_validate, qasr_set_phrases / qasr_get_phrases, qasr_phrase_tokenize.
 #include "engine_impl.h"
+#include "phrase_host.h"
 
 #include <set>
 
@@ -10,6 +12,8 @@ using namespace qasr;
 using namespace qasr::eng;
 
 static_assert(QASR_NGRAM_MAX == kConstrainNgramMax && QASR_BIAS_MAX == kConstrainBiasMax, "the header's limits are the kernels'");
+static_assert(QASR_PHRASE_MAX == kPhraseMax && QASR_PHRASE_LEN_MAX == kPhraseLenMax && kPhraseWalkMax == kPhraseLenMax - 1,
+              "the header's limits are the compiler's and the kernel's");
 
 // ------------------------------------------------------------------ ranges
 extern "C" int qasr_constraints_validate(const qasr_constraints *k, int vocab) {
@@ -37,6 +41,8 @@ static int ensure_constrain(qasr_ctx *c) {
     const size_t rows = (size_t)c->max_batch;
     qasr_ctx::ConstrainDev d;
     int rc;
+    if ((rc = dev_alloc(c, (void **)&d.ph, sizeof(PhraseTrie)))) return rc;
+    HIPCHK(hipMemset(d.ph, 0, sizeof(PhraseTrie)));
     if ((rc = dev_alloc(c, (void **)&d.prm, sizeof(ConstrainParams))) || (rc = dev_alloc(c, (void **)&d.ids, (size_t)QASR_BIAS_MAX * 4)) ||
         (rc = dev_alloc(c, (void **)&d.bias, (size_t)QASR_BIAS_MAX * 4)) || (rc = dev_alloc(c, (void **)&d.skey, rows * 8)) ||
         (rc = dev_alloc(c, (void **)&d.flag, rows * 4)) || (rc = dev_alloc(c, (void **)&d.gtok, rows * 4)))
@@ -46,21 +52,29 @@ static int ensure_constrain(qasr_ctx *c) {
     HIPCHK(hipMemset(d.skey, 0, rows * 8));
     HIPCHK(hipMemset(d.flag, 0, rows * 4));
     HIPCHK(hipMemset(d.gtok, 0, rows * 4));
+    const ConstrainParams neutral{0, 1.f, 1.f, 0, 0};
+    HIPCHK(hipMemcpy(d.prm, &neutral, sizeof neutral, hipMemcpyHostToDevice));
     c->cd = d;
+    return 0;
+}
+
+// constraints off: the parameters a stage that phrases keep on reads become the neutral ones
+static int constraints_off(qasr_ctx *c) {
+    const bool was_on = c->con.on;
+    c->con = qasr_ctx::ConstrainState();
+    if (!was_on || !c->cd.prm) return 0;   // (already off: the device holds the neutral parameters)
+    const ConstrainParams neutral{0, 1.f, 1.f, 0, 0};
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipMemcpy(c->cd.prm, &neutral, sizeof neutral, hipMemcpyHostToDevice));
     return 0;
 }
 
 extern "C" int qasr_set_constraints(qasr_ctx *c, const qasr_constraints *k) {
     if (!c) return fail(QASR_ERR_ARG, "null context");
-    if (!k) {   // off: no kernel, graph or result of the other paths changes
-        c->con = qasr_ctx::ConstrainState();
-        return 0;
-    }
+    if (!k) return constraints_off(c);   // off: no kernel, graph or result of the other paths changes
     if (int rc = qasr_constraints_validate(k, c->m->hp.vocab)) return rc;
-    if (k->no_repeat_ngram == 0 && k->repetition_penalty == 1.f && k->n_bias == 0) {
-        c->con = qasr_ctx::ConstrainState();
-        return 0;
-    }
+    if (k->no_repeat_ngram == 0 && k->repetition_penalty == 1.f && k->n_bias == 0) return constraints_off(c);
     if (c->m->hp.vocab > kConstrainVocabMax) return fail(QASR_ERR_STATE, "constraints: the model's vocabulary exceeds 2^20");
     HIPCHK(hipSetDevice(c->m->device));
     if (int rc = ensure_constrain(c)) return rc;
@@ -72,6 +86,7 @@ extern "C" int qasr_set_constraints(qasr_ctx *c, const qasr_constraints *k) {
     prm.n_bias = k->n_bias;
     // (device memory: a captured step serves any values)
     HIPCHK(hipStreamSynchronize(c->st));
+    c->con.on = true;   // (from here the device's parameters are no longer the neutral ones)
     HIPCHK(hipMemcpy(c->cd.prm, &prm, sizeof prm, hipMemcpyHostToDevice));
     if (k->n_bias) {
         HIPCHK(hipMemcpy(c->cd.ids, k->bias_ids, (size_t)k->n_bias * 4, hipMemcpyHostToDevice));
@@ -104,6 +119,97 @@ extern "C" int qasr_get_constraints(const qasr_ctx *c, qasr_constraints *out, in
     return 0;
 }
 
+// ------------------------------------------------------------------ phrases
+extern "C" int qasr_phrases_validate(const qasr_phrases *p, int vocab) {
+    if (!p) return fail(QASR_ERR_ARG, "phrases: null");
+    const std::string err = phrase_check(p->n_phrases, p->ids, p->len, p->boost, vocab);
+    return err.empty() ? 0 : fail(QASR_ERR_ARG, err);
+}
+
+extern "C" int qasr_set_phrases(qasr_ctx *c, const qasr_phrases *p) {
+    if (!c) return fail(QASR_ERR_ARG, "null context");
+    PhraseTrieHost tr;
+    if (p) {
+        if (int rc = qasr_phrases_validate(p, c->m->hp.vocab)) return rc;
+        const std::string err = phrase_compile(p->n_phrases, p->ids, p->len, p->boost, tr);
+        if (!err.empty()) return fail(QASR_ERR_ARG, err);
+    }
+    if (!p || p->n_phrases == 0) {   // off: the header a captured step reads says "no phrases"
+        const bool was_on = c->phr.on;
+        c->phr = qasr_ctx::PhraseState();
+        if (!was_on || !c->cd.ph) return 0;   // (already off: the header says so)
+        HIPCHK(hipSetDevice(c->m->device));
+        HIPCHK(hipStreamSynchronize(c->st));
+        HIPCHK(hipMemset(c->cd.ph, 0, sizeof(int)));   // (n_nodes, the first member)
+        return 0;
+    }
+    if (c->m->hp.vocab > kConstrainVocabMax) return fail(QASR_ERR_STATE, "phrases: the model's vocabulary exceeds 2^20");
+    HIPCHK(hipSetDevice(c->m->device));
+    if (int rc = ensure_constrain(c)) return rc;
+    if (!c->cd.ph_bonus) {   // (the last one allocated below)
+        qasr_ctx::ConstrainDev d = c->cd;
+        int rc;
+        if ((rc = dev_alloc(c, (void **)&d.ph_off, (size_t)(kPhraseNodeMax + 1) * 4)) || (rc = dev_alloc(c, (void **)&d.ph_tok, (size_t)kPhraseEdgeMax * 4)) ||
+            (rc = dev_alloc(c, (void **)&d.ph_dst, (size_t)kPhraseEdgeMax * 4)) || (rc = dev_alloc(c, (void **)&d.ph_bonus, (size_t)kPhraseEdgeMax * 4)))
+            return rc;
+        c->cd = d;
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipMemcpy(c->cd.ph_off, tr.child_off.data(), tr.child_off.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->cd.ph_tok, tr.tok.data(), tr.tok.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->cd.ph_dst, tr.dst.data(), tr.dst.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->cd.ph_bonus, tr.bonus.data(), tr.bonus.size() * 4, hipMemcpyHostToDevice));
+    const PhraseTrie hd{tr.nodes(), c->cd.ph_off, c->cd.ph_tok, c->cd.ph_dst, c->cd.ph_bonus};
+    c->phr.on = true;   // (from here the header names a list)
+    HIPCHK(hipMemcpy(c->cd.ph, &hd, sizeof hd, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(c->cd.skey, 0, (size_t)c->max_batch * 8));
+    HIPCHK(hipMemset(c->cd.flag, 0, (size_t)c->max_batch * 4));
+    size_t total = 0;
+    for (int k = 0; k < p->n_phrases; k++) total += (size_t)p->len[k];
+    c->phr.on = true;
+    c->phr.ids.assign(p->ids, p->ids + total);
+    c->phr.len.assign(p->len, p->len + p->n_phrases);
+    c->phr.boost.assign(p->boost, p->boost + p->n_phrases);
+    return 0;
+}
+
+extern "C" int qasr_get_phrases(const qasr_ctx *c, qasr_phrases *out, int32_t *ids, int32_t *len, float *boost, int cap_ids, int cap_phrases) {
+    if (!c || !out || cap_ids < 0 || cap_phrases < 0) return fail(QASR_ERR_ARG, "bad arguments");
+    const int n = (int)c->phr.len.size();
+    if (ids && cap_ids < (int)c->phr.ids.size()) return fail(QASR_ERR_ARG, "ids holds fewer entries than the phrases' tokens");
+    if ((len || boost) && cap_phrases < n) return fail(QASR_ERR_ARG, "len / boost hold fewer entries than the phrase list");
+    out->n_phrases = n;
+    out->ids = ids;
+    out->len = len;
+    out->boost = boost;
+    if (ids) std::copy(c->phr.ids.begin(), c->phr.ids.end(), ids);
+    if (len) std::copy(c->phr.len.begin(), c->phr.len.end(), len);
+    if (boost) std::copy(c->phr.boost.begin(), c->phr.boost.end(), boost);
+    return 0;
+}
+
+extern "C" int qasr_phrase_tokenize(const qasr_model *m, const char *text, int32_t *ids, int32_t *len, int cap_ids) {
+    if (!m || !text || !ids || !len || cap_ids < 0) return -fail(QASR_ERR_ARG, "bad arguments");
+    std::string s(text);
+    const char *ws = " \t\r\n\f\v";
+    const size_t b = s.find_first_not_of(ws);
+    if (b == std::string::npos) return -fail(QASR_ERR_ARG, "phrases: an empty hotword");
+    s = s.substr(b, s.find_last_not_of(ws) - b + 1);
+    std::vector<int32_t> v[2] = {m->tok.encode(s), m->tok.encode(s, true)};   // (the second: " " + text)
+    const int n = v[0] == v[1] ? 1 : 2;
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (v[i].empty()) return -fail(QASR_ERR_ARG, "phrases: an empty hotword");
+        if ((int)v[i].size() > QASR_PHRASE_LEN_MAX)
+            return -fail(QASR_ERR_ARG, "phrases: hotword \"" + s + "\" takes " + std::to_string(v[i].size()) + " tokens, a phrase holds 1..16");
+        if (at + v[i].size() > (size_t)cap_ids) return -fail(QASR_ERR_ARG, "phrases: ids holds fewer entries than the hotword's tokens");
+        std::copy(v[i].begin(), v[i].end(), ids + at);
+        at += v[i].size();
+        len[i] = (int32_t)v[i].size();
+    }
+    return n;
+}
+
 // --------------------------------------------------------- constraint stage
 int qasr::eng::constrain_step(qasr_ctx *c, int B, int src_div) {
     const int V = c->m->hp.vocab;
@@ -116,6 +222,7 @@ int qasr::eng::constrain_step(qasr_ctx *c, int B, int src_div) {
     a.skey = c->cd.skey; a.flag = c->cd.flag;
     a.tok = c->d_tok; a.hist = c->d_hist; a.gtok = c->cd.gtok;
     a.R = B; a.src_div = src_div;
+    a.ph = c->cd.ph;
     if (!launch_constrain(a, 0, c->st)) return fail(QASR_ERR_STATE, "constraints: the launcher declined " + std::to_string(B) + " rows");
     return 0;
 }

@@ -225,7 +225,18 @@ struct qasr_ctx {
         unsigned long long *skey = nullptr;
         int *flag = nullptr;
         int32_t *gtok = nullptr;
+        // hotword boosting: the trie's header lives with the state above (0 nodes until a list is
+        // set), so a step captured before the first qasr_set_phrases serves the lists that follow; the arrays it
+        // points to have a fixed capacity and are allocated by the first qasr_set_phrases
+        qasr::PhraseTrie *ph = nullptr;
+        int32_t *ph_off = nullptr, *ph_tok = nullptr, *ph_dst = nullptr;
+        float *ph_bonus = nullptr;
     } cd;
+    struct PhraseState {
+        bool on = false;
+        std::vector<int32_t> ids, len;
+        std::vector<float> boost;
+    } phr;
     int stage_t = 0;                   // constraints on: the history length of the rows of qasr_prefill* / qasr_decode_step
     long n_captures = 0;               // step graphs captured so far (option "graph_captures", read-only)
     DevBuf fork_args;                  // qasr_kv_fork: the caller's parent | from | to on the device
@@ -330,8 +341,8 @@ int ensure_beam(qasr_ctx *c);
 // graph key's first entry (a beam run's width, or 16 x the rows per clip of a sampling step)
 inline bool sampling_on(const qasr_ctx *c) { return c->samp.temperature > 0.f && !c->m->hp.aligner; }
 inline int sample_mul(const qasr_ctx *c) { return std::max(1, c->samp_run_N); }
-// decoding constraints: on for this context's decoding (aligner models ignore them)
-inline bool constraints_on(const qasr_ctx *c) { return c->con.on && !c->m->hp.aligner; }
+// decoding constraints or phrases: the constraint stage is on for this context's decoding (aligner models ignore them)
+inline bool constraints_on(const qasr_ctx *c) { return (c->con.on || c->phr.on) && !c->m->hp.aligner; }
 // (constraints on: 1024 on top, a key of its own beside every other mode's)
 inline int step_mode(const qasr_ctx *c) {
     return (c->beam_W >= 2 ? c->beam_W : sampling_on(c) ? 16 * sample_mul(c) : 0) + (constraints_on(c) ? 1024 : 0);

@@ -9,6 +9,7 @@
 // launch, and come back whole.  A launcher that takes no kernel is reported
 // as declined, never as success.
 #include "engine_impl.h"
+#include "phrase_host.h"
 
 using namespace qasr;
 using qasr::eng::fail;
@@ -416,7 +417,11 @@ extern "C" int qasr_kt_sample(int device, qasr_kt_sample_args *a) {
 }
 
 // ------------------------------------------------------- decoding constraints
-extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) {
+// qasr_kt_constrain and qasr_kt_phrases: the same call, the second with a phrase list (compiled here) and the
+// per-row record of which path chose the token
+namespace {
+template <class Args>
+int kt_constrain_run(int device, Args *a, const qasr_phrases *ph, int32_t *scanned_out) {
     if (!a) return fail(QASR_ERR_ARG, "bad arguments");
     if (a->R <= 0 || a->ld <= 0 || a->n_valid <= 0 || a->n_valid > a->ld || a->src_div < 1 || a->R % a->src_div != 0 || a->slices < 0 ||
         a->guard < 0 || a->launches < 1 || a->hist_stride < 1 || a->t < 0 || a->t >= a->hist_stride || !a->logits || !a->greedy || !a->hist ||
@@ -425,13 +430,20 @@ extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) {
     const qasr_constraints k{a->no_repeat_ngram, a->repetition_penalty, a->penalty_last_n, a->n_bias, a->bias_ids, a->bias};
     int rc;
     if ((rc = qasr_constraints_validate(&k, a->n_valid))) return rc;
+    PhraseTrieHost tr;
+    if (ph) {
+        if (!scanned_out) return fail(QASR_ERR_ARG, "bad arguments");
+        if ((rc = qasr_phrases_validate(ph, a->n_valid))) return rc;
+        const std::string err = phrase_compile(ph->n_phrases, ph->ids, ph->len, ph->boost, tr);
+        if (!err.empty()) return fail(QASR_ERR_ARG, err);
+    }
     const int R = a->R, RS = R / a->src_div, G = a->guard, HS = a->hist_stride;
     for (int r = 0; r < RS; r++)
         if (a->greedy[r] < 0 || a->greedy[r] >= a->n_valid) return fail(QASR_ERR_ARG, "greedy id outside [0, n_valid)");
     for (size_t i = 0; i < (size_t)R * HS; i++)
         if (a->hist[i] < 0 || a->hist[i] >= a->n_valid) return fail(QASR_ERR_ARG, "history id outside [0, n_valid)");
     if ((rc = use_device(device))) return rc;
-    KtBuf lg, gr, hs, prm, ids, bias, step, tok;
+    KtBuf lg, gr, hs, prm, ids, bias, step, tok, p_hd, p_off, p_tok, p_dst, p_bonus, scanned;
     KtFenced skey, flag;
     const ConstrainParams cp{a->no_repeat_ngram, a->repetition_penalty, 1.0f / a->repetition_penalty, a->penalty_last_n, a->n_bias};
     std::vector<int32_t> idv(QASR_BIAS_MAX, 0);
@@ -448,6 +460,21 @@ extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) {
         (rc = flag.put(rest_flag.data(), (size_t)RS * 4)))
         return rc;
     ConstrainArgs s{};
+    if (ph) {   // (an empty list: a header of 0 nodes, the arrays one unused entry each)
+        const std::vector<int32_t> none(1, 0);
+        const std::vector<int32_t> &off = tr.nodes() ? tr.child_off : none, &tk = tr.edges() ? tr.tok : none, &ds = tr.edges() ? tr.dst : none;
+        const std::vector<float> nob(1, 0.f);
+        const std::vector<float> &bo = tr.edges() ? tr.bonus : nob;
+        const std::vector<int32_t> unset(RS, -1);
+        if ((rc = put_state(p_off, off.data(), off.size() * 4)) || (rc = put_state(p_tok, tk.data(), tk.size() * 4)) ||
+            (rc = put_state(p_dst, ds.data(), ds.size() * 4)) || (rc = put_state(p_bonus, bo.data(), bo.size() * 4)) ||
+            (rc = put_state(scanned, unset.data(), (size_t)RS * 4)))
+            return rc;
+        const PhraseTrie hd{tr.nodes(), p_off.ptr<int32_t>(), p_tok.ptr<int32_t>(), p_dst.ptr<int32_t>(), p_bonus.ptr<float>()};
+        if ((rc = put_state(p_hd, &hd, sizeof hd))) return rc;
+        s.ph = p_hd.ptr<PhraseTrie>();
+        s.scanned = scanned.ptr<int>();
+    }
     s.logits = lg.ptr<float>(); s.ld = a->ld; s.n_valid = a->n_valid;
     s.greedy = gr.ptr<int32_t>();
     s.hist_in = hs.ptr<int32_t>(); s.hist_stride = HS; s.step = step.ptr<int>();
@@ -474,7 +501,16 @@ extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) {
         else if (hall[i] != (real ? a->hist[(size_t)row * HS + col] : -1)) return fail(QASR_ERR_STATE, "a write outside the history slot");
     }
     if ((rc = get(tok, a->tok)) || (rc = get(lg, a->logits_out)) || (rc = skey.take(a->skey_out, "the key scratch")) ||
-        (rc = flag.take(a->flag_out, "the flag scratch")))
+        (rc = flag.take(a->flag_out, "the flag scratch")) || (rc = get(scanned, scanned_out)))
         return rc;
     return 0;
+}
+}  // namespace
+
+extern "C" int qasr_kt_constrain(int device, qasr_kt_constrain_args *a) { return kt_constrain_run(device, a, nullptr, nullptr); }
+
+extern "C" int qasr_kt_phrases(int device, qasr_kt_phrases_args *a) {
+    if (!a) return fail(QASR_ERR_ARG, "bad arguments");
+    const qasr_phrases ph{a->n_phrases, a->ph_ids, a->ph_len, a->ph_boost};
+    return kt_constrain_run(device, a, &ph, a->scanned_out);
 }

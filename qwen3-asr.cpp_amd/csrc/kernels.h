@@ -528,12 +528,22 @@ void launch_sample_gumbel_dump(uint32_t n0, uint32_t n, float *out, hipStream_t 
 // q * src_div .. q * src_div + src_div - 1 (src_div = n_best at a hypothesis' first step, else 1) and is edited
 // once, by the history of its first token row.  The parameters and the bias list are device memory, so a captured
 // step serves any of their values.
+// Hotword boosting is step 2b of the same launch, between the bias and the ban: the phrase trie
+// (csrc/phrase_host.h compiles it) is read through a header in device memory, so a captured step serves any list,
+// and a header of 0 nodes (or a null `ph`) is "no phrases".
 constexpr int kConstrainNgramMax = 8, kConstrainBiasMax = 1024, kConstrainVocabMax = 1 << 20;
 struct ConstrainParams {
     int ngram;                           // 0 = off, else 1 .. kConstrainNgramMax
     float p, inv_p;                      // the penalty and 1.0f / p, rounded on the host (p == 1: off)
     int last_n;                          // the penalty's window (0: the whole history)
     int n_bias;                          // entries of bias_ids / bias in use
+};
+constexpr int kPhraseWalkMax = 15;       // the longest matched prefix (a phrase holds at most 16 tokens)
+struct PhraseTrie {
+    int n_nodes;                         // 0: no phrases
+    const int32_t *child_off;            // [n_nodes + 1]
+    const int32_t *tok, *dst;            // per edge: the token (ascending within a node), the node it leads to
+    const float *bonus;                  // per edge: eff of DESIGN.md §5.7
 };
 struct ConstrainArgs {
     float *logits; int ld, n_valid;      // [R / src_div][ld], edited in place
@@ -547,6 +557,8 @@ struct ConstrainArgs {
     int32_t *hist;                       // hist[r][*step] = tok[r] (may alias hist_in; null: not written)
     int32_t *gtok;                       // [R / src_div] out: the token per logits row (null: not written)
     int R, src_div;
+    const PhraseTrie *ph;                // [1] the phrase trie's header (null: no phrases)
+    int *scanned;                        // [R / src_div] out: the row took the scan (test only; null: not written)
 };
 // slices a row's scan is spread over where the caller passes 0
 int constrain_slices(int R, int n_valid);

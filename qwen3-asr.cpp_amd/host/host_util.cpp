@@ -374,11 +374,11 @@ static std::vector<std::string> utf8_chars(const std::string &s) {
 }
 
 // src/text_decoder.cpp:911-949 + :1077-1103
-std::vector<int32_t> Tokenizer::encode(const std::string &text) const {
+std::vector<int32_t> Tokenizer::encode(const std::string &text, bool lead_space) const {
     std::vector<int32_t> ids;
     std::istringstream iss(text);
     std::string word;
-    bool first = true;
+    bool first = !lead_space;
     const auto &b2u = bytes_to_unicode();
     while (iss >> word) {
         std::string w = first ? word : " " + word;

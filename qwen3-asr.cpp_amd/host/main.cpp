@@ -46,6 +46,10 @@ struct cli_params {
     float repetition_penalty = 1.f;
     std::vector<int32_t> suppress_tokens;
     std::vector<std::pair<int32_t, float>> token_bias;
+    // --hotword / --hotwords-file / --hotword-boost: hotword boosting (a boost <= 0: --hotword-boost's)
+    std::vector<std::string> hotwords;
+    std::vector<float> hotword_boosts;
+    float hotword_boost = 5.f;
     std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
 };
@@ -75,6 +79,9 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --penalty-last-n <n>   With --repetition-penalty: only the last n tokens count (0: all)\n");
     fprintf(stderr, "  --suppress-tokens <id,id,...>  Token ids never emitted\n");
     fprintf(stderr, "  --token-bias <id:val,...>  Add val to the logit of token id before every choice\n");
+    fprintf(stderr, "  --hotword <text>       Prefer this word or phrase (repeatable; at most 16 tokens each)\n");
+    fprintf(stderr, "  --hotwords-file <path> One hotword a line, optionally a tab and its own boost; lines starting with # are comments\n");
+    fprintf(stderr, "  --hotword-boost <b>    Added to the next token's logit while a hotword is being spelled, 0 < b <= 100 (default 5)\n");
     fprintf(stderr, "  --score <text>         Score <text> as a transcript of the -f file instead of transcribing (repeatable):\n");
     fprintf(stderr, "                         per text the summed log-probability, the mean per token and the token count\n");
     fprintf(stderr, "                         (the EOS included); with --tokens every token's id, text and log-probability,\n");
@@ -172,6 +179,43 @@ static bool parse(int argc, char **argv, cli_params &p) {
             if (!val(v)) return false;
             p.repetition_penalty = (float)atof(v.c_str());
             if (!(p.repetition_penalty > 0.f && p.repetition_penalty <= 10.f)) { fprintf(stderr, "Error: --repetition-penalty takes 0 < p <= 10\n"); return false; }
+        }
+        else if (!strcmp(a, "--hotword")) {
+            if (!val(v)) return false;
+            if (v.find_first_not_of(" \t\r\n") == std::string::npos) { fprintf(stderr, "Error: --hotword takes a non-empty text\n"); return false; }
+            p.hotwords.push_back(v);
+            p.hotword_boosts.push_back(0.f);
+        }
+        else if (!strcmp(a, "--hotword-boost")) {
+            if (!val(v)) return false;
+            char *tail = nullptr;
+            p.hotword_boost = strtof(v.c_str(), &tail);
+            if (*tail != 0 || !(p.hotword_boost > 0.f && p.hotword_boost <= 100.f)) { fprintf(stderr, "Error: --hotword-boost takes 0 < b <= 100\n"); return false; }
+        }
+        else if (!strcmp(a, "--hotwords-file")) {
+            if (!val(v)) return false;
+            std::ifstream f(v);
+            if (!f) { fprintf(stderr, "Error: cannot read hotwords file %s\n", v.c_str()); return false; }
+            int no = 0;
+            for (std::string line; std::getline(f, line);) {
+                no++;
+                while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+                if (line.empty() || line[0] == '#') continue;
+                float b = 0.f;
+                const size_t tab = line.find('\t');
+                if (tab != std::string::npos) {
+                    char *tail = nullptr;
+                    b = strtof(line.c_str() + tab + 1, &tail);
+                    if (tail == line.c_str() + tab + 1 || *tail != 0 || !(b > 0.f && b <= 100.f)) {
+                        fprintf(stderr, "Error: %s line %d: the boost after the tab takes 0 < b <= 100\n", v.c_str(), no);
+                        return false;
+                    }
+                    line.resize(tab);
+                }
+                if (line.find_first_not_of(" \t") == std::string::npos) { fprintf(stderr, "Error: %s line %d: no text before the boost\n", v.c_str(), no); return false; }
+                p.hotwords.push_back(line);
+                p.hotword_boosts.push_back(b);
+            }
         }
         else if (!strcmp(a, "--penalty-last-n")) {
             if (!val(v)) return false;
@@ -517,6 +561,9 @@ static int run_transcription(const cli_params &p) {
     tp.penalty_last_n = p.penalty_last_n;
     tp.suppress_tokens = p.suppress_tokens;
     tp.token_bias = p.token_bias;
+    tp.hotwords = p.hotwords;
+    tp.hotword_boost = p.hotword_boost;
+    tp.hotword_boosts = p.hotword_boosts;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));

@@ -63,7 +63,8 @@ public:
     bool load(const GGUFFile &f, std::string &err);
     std::string decode(const std::vector<int32_t> &ids) const;
     std::string decode_token(int32_t id) const;
-    std::vector<int32_t> encode(const std::string &text) const;
+    // lead_space: the first word too carries the leading-space marker (the text as it stands after other words)
+    std::vector<int32_t> encode(const std::string &text, bool lead_space = false) const;
     // one word, no leading-space marker; unknown subwords are skipped with a
     // warning (src/forced_aligner.cpp:1589-1603)
     std::vector<int32_t> encode_word(const std::string &word) const;

@@ -146,7 +146,8 @@ bool Qwen3ASR::set_sampling(const transcribe_params &params) {
 
 // decoding constraints as the call asks (qasr_set_constraints: no graph is dropped either way)
 static bool constraints_asked(const transcribe_params &params) {
-    return params.no_repeat_ngram != 0 || params.repetition_penalty != 1.f || !params.suppress_tokens.empty() || !params.token_bias.empty();
+    return params.no_repeat_ngram != 0 || params.repetition_penalty != 1.f || !params.suppress_tokens.empty() || !params.token_bias.empty() ||
+           !params.hotwords.empty();
 }
 
 bool Qwen3ASR::set_constraints(const transcribe_params &params) {
@@ -163,6 +164,32 @@ bool Qwen3ASR::set_constraints(const transcribe_params &params) {
     qasr_constraints k{params.no_repeat_ngram, params.repetition_penalty, params.penalty_last_n, (int32_t)ids.size(), ids.data(), bias.data()};
     if (qasr_set_constraints(ctx_, constraints_asked(params) ? &k : nullptr) != 0) {
         error_msg_ = std::string("Failed to set decoding constraints: ") + qasr_last_error();
+        return false;
+    }
+    return true;
+}
+
+// hotwords as the call asks (qasr_set_phrases: every text in both tokenisations)
+bool Qwen3ASR::set_hotwords(const transcribe_params &params) {
+    std::vector<int32_t> ids, len;
+    std::vector<float> boost;
+    for (size_t i = 0; i < params.hotwords.size(); i++) {
+        int32_t v[2 * QASR_PHRASE_LEN_MAX], l[2];
+        const int n = qasr_phrase_tokenize(model_, params.hotwords[i].c_str(), v, l, 2 * QASR_PHRASE_LEN_MAX);
+        if (n < 0) {
+            error_msg_ = std::string("Failed to tokenize hotword \"") + params.hotwords[i] + "\": " + qasr_last_error();
+            return false;
+        }
+        const float b = i < params.hotword_boosts.size() && params.hotword_boosts[i] > 0.f ? params.hotword_boosts[i] : params.hotword_boost;
+        for (int k = 0, at = 0; k < n; at += l[k], k++) {
+            ids.insert(ids.end(), v + at, v + at + l[k]);
+            len.push_back(l[k]);
+            boost.push_back(b);
+        }
+    }
+    const qasr_phrases p{(int32_t)len.size(), ids.data(), len.data(), boost.data()};
+    if (qasr_set_phrases(ctx_, len.empty() ? nullptr : &p) != 0) {
+        error_msg_ = std::string("Failed to set hotwords: ") + qasr_last_error();
         return false;
     }
     return true;
@@ -220,7 +247,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     const int NB = sampling ? std::max(params.n_best, 1) : 1;
     const bool many = sampling && NB >= 2;
     if (!ensure_ctx(B * std::max(W, NB), maxP + (int)sys.size() + params.max_tokens) || !set_logprobs(params.token_logprobs) ||
-        !set_top_k(params.top_k) || !set_beam_width(params.beam_width) || !set_sampling(params) || !set_constraints(params)) {
+        !set_top_k(params.top_k) || !set_beam_width(params.beam_width) || !set_sampling(params) || !set_constraints(params) || !set_hotwords(params)) {
         for (auto &r : out) r.error_msg = error_msg_;
         return out;
     }
@@ -432,9 +459,9 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     const int S = slots > 0 ? std::min(slots, max_batch_) : max_batch_;
     if (params.beam_width >= 2) { error_msg_ = "The stream has no beam search (transcribe_params::beam_width)"; return false; }
     if (params.temperature > 0.f) { error_msg_ = "The stream has no sampling (transcribe_params::temperature)"; return false; }
-    if (constraints_asked(params)) { error_msg_ = "The stream has no decoding constraints (transcribe_params::no_repeat_ngram ...)"; return false; }
+    if (constraints_asked(params)) { error_msg_ = "The stream has neither decoding constraints nor hotwords (transcribe_params::no_repeat_ngram ... hotwords)"; return false; }
     if (!ensure_ctx(S, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) || !set_beam_width(0) ||
-        !set_sampling(params) || !set_constraints(params))
+        !set_sampling(params) || !set_constraints(params) || !set_hotwords(params))
         return false;
     qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
     qasr_set_profile(ctx_, profile_ ? 1 : 0);   // the report covers the whole stream

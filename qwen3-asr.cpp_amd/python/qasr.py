@@ -40,6 +40,7 @@ EXPORTS = [
     "qasr_prefill_score", "qasr_score",
     "qasr_set_sampling", "qasr_get_sampling", "qasr_set_sample_streams", "qasr_get_samples",
     "qasr_constraints_validate", "qasr_set_constraints", "qasr_get_constraints",
+    "qasr_phrases_validate", "qasr_set_phrases", "qasr_get_phrases", "qasr_phrase_tokenize",
 ]
 
 
@@ -75,10 +76,18 @@ class Constraints(C.Structure):
                 ("n_bias", C.c_int32), ("bias_ids", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float))]
 
 
+class Phrases(C.Structure):
+    """qasr_phrases"""
+    _fields_ = [("n_phrases", C.c_int32), ("ids", C.POINTER(C.c_int32)), ("len", C.POINTER(C.c_int32)),
+                ("boost", C.POINTER(C.c_float))]
+
+
 QASR_BEAM_MAX = 8
 QASR_SAMPLE_MAX = 8
 QASR_NGRAM_MAX = 8
 QASR_BIAS_MAX = 1024
+QASR_PHRASE_MAX = 4096
+QASR_PHRASE_LEN_MAX = 16
 _lib = None
 # void (*)(void *user, int seq, int n_generated, int32_t token)
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int32)
@@ -147,6 +156,10 @@ def lib() -> C.CDLL:
             "qasr_constraints_validate": ([C.POINTER(Constraints), I], I),
             "qasr_set_constraints": ([P, C.POINTER(Constraints)], I),
             "qasr_get_constraints": ([P, C.POINTER(Constraints), I32P, F, I], I),
+            "qasr_phrases_validate": ([C.POINTER(Phrases), I], I),
+            "qasr_set_phrases": ([P, C.POINTER(Phrases)], I),
+            "qasr_get_phrases": ([P, C.POINTER(Phrases), I32P, I32P, F, I, I], I),
+            "qasr_phrase_tokenize": ([P, C.c_char_p, I32P, I32P, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -195,6 +208,37 @@ def constraints_validate(vocab: int = 0, **kw) -> None:
     """qasr_constraints_validate (host only): raises QasrError naming the violated range"""
     k, _keep = make_constraints(**kw)
     _check(lib().qasr_constraints_validate(C.byref(k), int(vocab)), "qasr_constraints_validate")
+
+
+def make_phrases(phrases, boost: float = 5.0, tokenize=None):
+    """a qasr_phrases from Python values, with the arrays it points into (keep them alive as long as it is used).
+    Each phrase is a list of ids, an (ids, boost) pair or a string; a string goes through `tokenize` (text ->
+    list of id lists: Model.phrase_tokenize) and yields every variant; `boost` is the boost of a phrase without
+    its own"""
+    ids, lens, val = [], [], []
+    for ph in phrases or ():
+        b = float(boost)
+        if isinstance(ph, tuple) and len(ph) == 2 and not isinstance(ph[0], (int, np.integer)):
+            ph, b = ph[0], float(ph[1])
+        if isinstance(ph, str):
+            if tokenize is None:
+                raise QasrError("a phrase given as text needs the model's tokenizer")
+            variants = tokenize(ph)
+        else:
+            variants = [[int(x) for x in ph]]
+        for v in variants:
+            ids += v
+            lens.append(len(v))
+            val.append(b)
+    a_ids, a_len, a_val = np.array(ids or [0], np.int32), np.array(lens or [0], np.int32), np.array(val or [0], np.float32)
+    p = Phrases(len(lens), _i32(a_ids), _i32(a_len), _f(a_val))
+    return p, (a_ids, a_len, a_val)
+
+
+def phrases_validate(phrases, boost: float = 5.0, vocab: int = 0) -> None:
+    """qasr_phrases_validate (host only): raises QasrError naming the violated range"""
+    p, _keep = make_phrases(phrases, boost)
+    _check(lib().qasr_phrases_validate(C.byref(p), int(vocab)), "qasr_phrases_validate")
 
 
 def _check(rc: int, what: str) -> None:
@@ -313,6 +357,19 @@ class Model:
         lib().qasr_tokenize(self.h, text.encode(), _i32(a), n)
         return a[:n].tolist()
 
+
+    def phrase_tokenize(self, text: str) -> List[List[int]]:
+        """qasr_phrase_tokenize: the tokenisations a hotword needs, of the trimmed text and of " " + text (one
+        where they are equal)"""
+        ids, ln = np.zeros(2 * QASR_PHRASE_LEN_MAX, np.int32), np.zeros(2, np.int32)
+        n = lib().qasr_phrase_tokenize(self.h, text.encode(), _i32(ids), _i32(ln), len(ids))
+        if n < 0:
+            raise QasrError(f"qasr_phrase_tokenize: {lib().qasr_last_error().decode(errors='replace')}")
+        out, at = [], 0
+        for i in range(n):
+            out.append(ids[at:at + ln[i]].tolist())
+            at += int(ln[i])
+        return out
 
     # ---- forced aligner (Qwen3-ForcedAligner files) -------------------------
     @property
@@ -622,6 +679,22 @@ class Context:
         return {"no_repeat_ngram": int(k.no_repeat_ngram), "repetition_penalty": float(k.repetition_penalty),
                 "penalty_last_n": int(k.penalty_last_n),
                 "bias": {int(i): float(b) for i, b in zip(ids[:k.n_bias], bias[:k.n_bias])}}
+
+    def set_phrases(self, phrases=None, boost: float = 5.0) -> None:
+        """qasr_set_phrases: hotwords the decoder prefers.  Each phrase is a list of token ids,
+        an (ids, boost) pair or a string (tokenised by the model, with and without a leading space); None or an
+        empty list turns phrases off"""
+        p, _keep = make_phrases(phrases, boost, self.model.phrase_tokenize)
+        _check(lib().qasr_set_phrases(self.h, C.byref(p)), "qasr_set_phrases")
+
+    def get_phrases(self) -> list:
+        """qasr_get_phrases: the list in force as [(ids, boost)]"""
+        ids, ln = np.zeros(QASR_PHRASE_MAX * QASR_PHRASE_LEN_MAX, np.int32), np.zeros(QASR_PHRASE_MAX, np.int32)
+        val = np.zeros(QASR_PHRASE_MAX, np.float32)
+        p = Phrases()
+        _check(lib().qasr_get_phrases(self.h, C.byref(p), _i32(ids), _i32(ln), _f(val), len(ids), len(ln)), "qasr_get_phrases")
+        at = np.concatenate([[0], np.cumsum(ln[:p.n_phrases])])
+        return [(ids[at[k]:at[k + 1]].tolist(), float(val[k])) for k in range(p.n_phrases)]
 
     def _sampling_on(self) -> bool:
         return self.get_sampling().temperature > 0 and not self.model.is_aligner
