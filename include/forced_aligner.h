@@ -65,6 +65,9 @@ public:
 
     // MI355X addition: device selection
     void set_device(int device) { device_ = device; }
+    // MI355X addition (default off): align(audio_path) takes a file at any rate the resampler supports
+    // (qasr_resample of qasr_capi.h) and resamples it to 16 kHz on the device; off, such a file is an error
+    void set_resample(bool on) { resample_ = on; }
 
 private:
     bool ensure_ctx(int n_ctx);
@@ -72,6 +75,7 @@ private:
     qasr_model *model_ = nullptr;
     qasr_ctx *ctx_ = nullptr;
     int ctx_len_ = 0, device_ = 0;
+    bool resample_ = false;
     forced_aligner_hparams hparams_;
     std::string error_msg_;
 };

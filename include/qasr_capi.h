@@ -859,6 +859,64 @@ typedef struct {
 } qasr_kt_phrases_args;
 int qasr_kt_phrases(int device, qasr_kt_phrases_args *a);
 
+/* ---- audio at other sample rates: the resampler to 16 kHz ----------------
+ * Every other entry point takes 16 kHz mono float PCM.  The *_rate entry points take a rate per
+ * clip and resample on the device, in front of the mel stage, by one rule (csrc/resample_host.h
+ * states it in full): a polyphase Kaiser-windowed sinc with L = 16000 / gcd, M = rate / gcd,
+ * Z = 32 zero crossings a side, BETA = 9, cut-off 0.96 x the lower Nyquist, fp32 taps, fp64
+ * accumulation in tap order.  The device result equals the host rule bit for bit for finite
+ * input.  A clip at 16000 is copied unchanged.  Supported: 4000 <= rate <= 192000 with
+ * L <= 640 (8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400,
+ * 192000, ...); any other rate is QASR_ERR_ARG with the rate in qasr_last_error().
+ * `rate` may be NULL: every clip is at 16000 (the call is then the plain one).
+ *
+ * host only (no device is touched):
+ *   qasr_resample_plan   L, M and H (taps a phase = 2H + 1) of a rate; 16000: 1, 1, 0
+ *   qasr_resample_len    output samples of n_in input samples, (n_in * L + M - 1) / M; minus an
+ *                        error code for an unsupported rate, n_in < 0 or a result past INT_MAX
+ *   qasr_resample_taps   the table h[L][2H + 1] into out (cap floats); returns its size (cap 0:
+ *                        the size alone), or minus an error code
+ *   qasr_resample_host   the rule on the CPU: out receives qasr_resample_len(n, rate) samples;
+ *                        returns that count, or minus an error code
+ * stage level, as qasr_mel (host buffers in and out, synchronises):
+ *   qasr_resample        B clips -> out, the resampled clips back to back
+ *   qasr_resample_last_us  device time of the last qasr_resample's kernel launch on this context, in
+ *                        microseconds (HIP events around the launch alone), or minus an error code
+ * whole path:
+ *   qasr_stage_audio_rate       as qasr_stage_audio; the pool then holds the 16 kHz clips, so
+ *                               qasr_run, qasr_run_staged, qasr_score and qasr_run_stream_staged
+ *                               serve it unchanged
+ *   qasr_transcribe_batch_rate  qasr_stage_audio_rate + qasr_run
+ *   qasr_run_stream_rate        qasr_run_stream whose fetch also returns the clip's rate; prompt
+ *                               and context checks use the resampled length, and an unsupported
+ *                               rate fails that clip alone through the sink */
+int qasr_resample_plan(int rate, int *L, int *M, int *H);
+int qasr_resample_len(int n_in, int rate);
+int qasr_resample_taps(int rate, float *out, int cap);
+int qasr_resample_host(const float *pcm, int n, int rate, float *out);
+int qasr_resample(qasr_ctx *c, const float *const *pcm, const int *n, const int *rate, int B, float *out);
+int qasr_resample_last_us(qasr_ctx *c);
+int qasr_stage_audio_rate(qasr_ctx *c, const float *const *pcm, const int *n, const int *rate, int B);
+int qasr_transcribe_batch_rate(qasr_ctx *c, const float *const *pcm, const int *n, const int *rate, int B,
+                               int max_tokens, int ignore_eos, int32_t *tokens, int *n_tokens, qasr_timings *t);
+typedef int (*qasr_fetch_rate_fn)(void *user, const float **pcm, int *n_samples, int *rate, int *max_tokens);
+int qasr_run_stream_rate(qasr_ctx *c, int slots, qasr_fetch_rate_fn fetch, qasr_sink_fn sink, void *user,
+                         int max_tokens, int ignore_eos, qasr_stream_stats *stats);
+
+/* test only: the resample kernel on B packed clips (pcm: the raw clips back to back, n_in / rate [B]) with the
+ * library's tap tables.  The device input is followed by `guard` floats of 0xFF bytes (NaN); out receives, per
+ * clip, `guard` floats of 0xFF, the clip's qasr_resample_len outputs and `guard` floats of 0xFF again
+ * ([sum n_out + 2 * guard * B] floats).  launches 2: a second launch on the same device state into out2.
+ * tile receives the outputs a workgroup computes. */
+typedef struct {
+    int32_t B, guard, launches;
+    const int32_t *n_in, *rate;
+    const float *pcm;
+    float *out, *out2;
+    int32_t tile;
+} qasr_kt_resample_args;
+int qasr_kt_resample(int device, qasr_kt_resample_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ struct transcribe_params {
     std::vector<std::string> hotwords;
     float hotword_boost = 5.f;
     std::vector<float> hotword_boosts;
+    // MI355X addition (trailing, default off): transcribe(audio_path) takes a file at any rate the resampler supports
+    // (qasr_stage_audio_rate of qasr_capi.h: 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4, 192 kHz ...)
+    // and resamples it to 16 kHz on the device, in front of the mel stage; off, such a file is an error
+    bool resample = false;
 };
 
 // MI355X addition: one hypothesis of a beam run
@@ -159,6 +163,14 @@ public:
     bool transcribe_stream(const std::function<bool(int &id, std::vector<float> &pcm)> &fetch,
                            const std::function<void(int id, transcribe_result result)> &sink,
                            const transcribe_params &params = transcribe_params(), int n_ctx = 0, int slots = 0);
+    // MI355X additions: the same three for clips at other sample rates (one rate per clip), resampled to 16 kHz on
+    // the device (qasr_transcribe_batch_rate / qasr_run_stream_rate); an unsupported rate fails its clip alone
+    transcribe_result transcribe(const float *samples, int n_samples, int sample_rate, const transcribe_params &params = transcribe_params());
+    std::vector<transcribe_result> transcribe_batch(const std::vector<std::vector<float>> &clips, const std::vector<int> &rates,
+                                                    const transcribe_params &params = transcribe_params());
+    bool transcribe_stream_rate(const std::function<bool(int &id, std::vector<float> &pcm, int &rate)> &fetch,
+                                const std::function<void(int id, transcribe_result result)> &sink,
+                                const transcribe_params &params = transcribe_params(), int n_ctx = 0, int slots = 0);
     void set_max_batch(int slots) { max_batch_ = slots > 0 ? slots : 1; }
     int max_batch() const { return max_batch_; }
     void set_profile(bool on) { profile_ = on; }
@@ -173,7 +185,7 @@ public:
                                     const transcribe_params &params = transcribe_params());
 
 private:
-    transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params);
+    transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params, int sample_rate = 0);
     bool ensure_ctx(int batch, int n_ctx);
     bool set_logprobs(bool on);
     bool set_top_k(int k);
@@ -181,7 +193,13 @@ private:
     bool set_sampling(const transcribe_params &params);
     bool set_constraints(const transcribe_params &params);
     bool set_hotwords(const transcribe_params &params);
-    std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params);
+    std::vector<transcribe_result> transcribe_run(const std::vector<std::vector<float>> &clips, const transcribe_params &params,
+                                                  const std::vector<int> *rates = nullptr);
+    std::vector<transcribe_result> batch_impl(const std::vector<std::vector<float>> &clips, const std::vector<int> *rates,
+                                              const transcribe_params &params);
+    bool stream_impl(const std::function<bool(int &id, std::vector<float> &pcm, int &rate)> &fetch, bool with_rates,
+                     const std::function<void(int id, transcribe_result result)> &sink, const transcribe_params &params, int n_ctx,
+                     int slots);
 
     qasr_model *model_ = nullptr;
     qasr_ctx *ctx_ = nullptr;

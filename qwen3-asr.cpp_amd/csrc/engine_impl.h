@@ -11,6 +11,7 @@
 //   engine_constrain.hip  decoding constraints: qasr_set_constraints, the constraint stage of a prefill or decode step
 //   engine_score.hip   teacher-forced scoring: the score head over prefill rows, qasr_prefill_score, qasr_score
 //   engine_align.hip   the forced aligner and its JSON output
+//   engine_resample.hip  audio at other rates: the host-only resampler entries, the tap-table cache, the resample stage
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@
 #include "../host/qasr_host.h"
 #include "beam_host.h"
 #include "score_host.h"
+#include "resample_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -104,6 +106,12 @@ struct DevBuf {
     void *p = nullptr;
     size_t n = 0;
     template <class T> T *as() const { return (T *)p; }
+};
+
+// the resampler's plan of a rate and its table on the device (kernels.h ResampleClip's layout; null for the copy)
+struct ResampleTab {
+    qasr::ResamplePlan pl;
+    float *d_taps = nullptr;
 };
 
 struct qasr_ctx {
@@ -243,6 +251,12 @@ struct qasr_ctx {
     // teacher-forced scoring (engine_score.hip): the gathered normed rows (fp16), row indices | targets, the three
     // outputs of a block of rows, the score head's scratch
     DevBuf sc_rows, sc_tab, sc_out, sc_scratch;
+    // resampler to 16 kHz (engine_resample.hip): the raw clips of a call, its clip and block lists,
+    // and the tap tables by rate, each built the first time a clip at that rate arrives
+    DevBuf rsin, rsclips, rsblocks;
+    std::map<int, ResampleTab> rs_tabs;
+    bool rs_timed = false;
+    hipEvent_t rs_ev[2] = {};          // around qasr_resample's launch (qasr_resample_last_us), created by its first call
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -312,6 +326,7 @@ struct qasr_ctx {
         for (auto &e : step_ev) (void)hipEventDestroy(e);
         for (auto &b : owned) (void)hipFree(b.p);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : rs_ev) if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
         if (st) (void)hipStreamDestroy(st);
     }
@@ -428,6 +443,16 @@ int constrain_step(qasr_ctx *c, int B, int src_div);
 int greedy_loop(qasr_ctx *c, int B, int max_tokens, int ignore_eos, std::vector<int32_t> &hist, int &steps);
 int run_results(qasr_ctx *c, int B, int max_tokens, int ignore_eos, const std::vector<int32_t> &hist, int steps, int32_t *tokens,
                 int *n_tokens, qasr_timings *t);
+
+// engine_resample.hip
+struct ResampleLayout {
+    std::vector<long> in_off, out_off;   // per clip: first raw sample, first resampled sample
+    std::vector<int> n_in, n_out, rate;
+    long in_tot = 0, out_tot = 0;
+};
+int resample_table(qasr_ctx *c, int rate, ResampleTab &out);
+int resample_layout(const int *n, const int *rate, int B, ResampleLayout &o);
+int run_resample(qasr_ctx *c, const ResampleLayout &o, const float *d_in, float *d_out, bool timed = false);
 
 // engine_decode.hip
 int split_bucket(qasr_ctx *c, int pos);

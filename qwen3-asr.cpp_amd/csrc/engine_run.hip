@@ -336,9 +336,10 @@ struct StreamSlot {
 }  // namespace
 
 // next(clip) -> false when the queue is empty; a clip is host samples (pcm, n)
-// or a clip of the staged pool (staged >= 0)
+// or a clip of the staged pool (staged >= 0); host samples may come at another rate (qasr_run_stream_rate), which
+// the refill resamples on the device
 struct StreamClip {
-    int id = -1, budget = 0, n = 0, staged = -1;
+    int id = -1, budget = 0, n = 0, staged = -1, rate = qasr::kResampleOutRate;
     const float *pcm = nullptr;
 };
 static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamClip &)> &next, qasr_sink_fn sink, void *user,
@@ -415,6 +416,8 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
             if (c->fuse.refill_group > 0 && (int)freeS.size() > c->fuse.refill_group) freeS.resize(c->fuse.refill_group);
             const auto t0 = std::chrono::steady_clock::now();
             std::vector<int> ids, ns, budgets, slots;
+            std::vector<int> raw_n, rates;   // host clips as fetched; ns holds their lengths at 16 kHz
+            bool resample = false;
             std::vector<float> pcm;   // host clips of this refill, packed (-> c->spcm)
             std::vector<long> off;
             bool staged = false;
@@ -426,6 +429,10 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                 if (k.staged >= 0) {
                     if (k.staged >= (int)c->staged_n.size()) { reject(id, QASR_ERR_ARG, "staged clip index out of range"); continue; }
                     k.n = c->staged_n[k.staged];
+                }
+                const int raw = k.n;
+                if (k.staged < 0 && k.rate != qasr::kResampleOutRate && k.n >= 0) {   // every check below sees the output length
+                    if ((k.n = qasr_resample_len(raw, k.rate)) < 0) { const std::string why = qasr_last_error(); reject(id, QASR_ERR_ARG, why.c_str()); continue; }
                 }
                 const int P = qasr_prompt_len(encoder_frames(mel_frames(std::max(k.n, 0)))) + (int)c->sys_ids.size();
                 if (k.n < 0 || (k.staged < 0 && k.n > 0 && !k.pcm) || k.budget <= 0) { reject(id, QASR_ERR_ARG, "bad clip (length, samples or budget)"); continue; }
@@ -439,13 +446,24 @@ static int run_stream(qasr_ctx *c, int slots, const std::function<bool(StreamCli
                     off.push_back(c->staged_off[k.staged]);
                 } else {
                     off.push_back((long)pcm.size());
-                    pcm.insert(pcm.end(), k.pcm, k.pcm + k.n);
+                    pcm.insert(pcm.end(), k.pcm, k.pcm + raw);
+                    raw_n.push_back(raw);
+                    rates.push_back(k.rate);
+                    resample = resample || k.rate != qasr::kResampleOutRate;
                 }
                 slots.push_back(freeS[ids.size() - 1]);
             }
             if (ids.empty()) return 0;
             const int R = (int)ids.size();
-            if (!staged) {
+            if (!staged && resample) {   // raw clips -> c->rsin, resampled (16 kHz clips copied) into c->spcm
+                ResampleLayout lay;
+                if ((rc = resample_layout(raw_n.data(), rates.data(), R, lay)) || (rc = ensure(c, c->rsin, std::max<size_t>(pcm.size(), 1) * 4)) ||
+                    (rc = ensure(c, c->spcm, std::max<long>(lay.out_tot, 1) * 4)))
+                    return rc;
+                HIPCHK(hipMemcpyAsync(c->rsin.p, pcm.data(), pcm.size() * 4, hipMemcpyHostToDevice, s));
+                if ((rc = run_resample(c, lay, c->rsin.as<float>(), c->spcm.as<float>()))) return rc;
+                off = lay.out_off;
+            } else if (!staged) {
                 if ((rc = ensure(c, c->spcm, std::max<size_t>(pcm.size(), 1) * 4))) return rc;
                 HIPCHK(hipMemcpyAsync(c->spcm.p, pcm.data(), pcm.size() * 4, hipMemcpyHostToDevice, s));
             }
@@ -577,6 +595,13 @@ extern "C" int qasr_run_stream(qasr_ctx *c, int slots, qasr_fetch_fn fetch, qasr
     if (!fetch) return fail(QASR_ERR_ARG, "bad arguments");
     return run_stream(c, slots, [&](StreamClip &k) { return (k.id = fetch(user, &k.pcm, &k.n, &k.budget)) >= 0; }, sink, user,
                       max_tokens, ignore_eos, stats);
+}
+
+extern "C" int qasr_run_stream_rate(qasr_ctx *c, int slots, qasr_fetch_rate_fn fetch, qasr_sink_fn sink, void *user, int max_tokens,
+                                    int ignore_eos, qasr_stream_stats *stats) {
+    if (!fetch) return fail(QASR_ERR_ARG, "bad arguments");
+    return run_stream(c, slots, [&](StreamClip &k) { return (k.id = fetch(user, &k.pcm, &k.n, &k.rate, &k.budget)) >= 0; }, sink,
+                      user, max_tokens, ignore_eos, stats);
 }
 
 extern "C" int qasr_run_stream_staged(qasr_ctx *c, int slots, qasr_fetch_staged_fn fetch, qasr_sink_fn sink, void *user,

@@ -514,3 +514,59 @@ extern "C" int qasr_kt_phrases(int device, qasr_kt_phrases_args *a) {
     const qasr_phrases ph{a->n_phrases, a->ph_ids, a->ph_len, a->ph_boost};
     return kt_constrain_run(device, a, &ph, a->scanned_out);
 }
+
+// the resampler (csrc/resample.hip) on B packed clips at mixed rates, with the library's tap tables.  The packed
+// input is followed by `guard` floats of 0xFF bytes; every clip's output has `guard` floats of 0xFF before and after
+// it, and the whole buffer ([sum n_out + 2 * guard * B]) comes back.  launches == 2: a second launch on the same
+// inputs, clip list and tables into out2, laid out the same.
+extern "C" int qasr_kt_resample(int device, qasr_kt_resample_args *a) {
+    if (!a || a->B <= 0 || a->guard < 0 || !a->n_in || !a->rate || !a->out || a->launches < 1 || a->launches > 2 ||
+        (a->launches == 2 && !a->out2))
+        return fail(QASR_ERR_ARG, "bad arguments");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int B = a->B, G = a->guard;
+    eng::ResampleLayout o;
+    if ((rc = eng::resample_layout(a->n_in, a->rate, B, o))) return rc;
+    if (o.in_tot > 0 && !a->pcm) return fail(QASR_ERR_ARG, "bad arguments");
+    std::vector<KtBuf> tabs(B);
+    std::vector<ResampleClip> clips(B);
+    std::vector<int2> blocks;
+    for (int b = 0; b < B; b++) {
+        ResamplePlan pl;
+        (void)resample_plan(o.rate[b], pl);   // (resample_layout refused the unsupported ones)
+        if (!resample_fits(pl.L, pl.M, pl.H)) return fail(QASR_ERR_STATE, "the kernel's window does not hold this rate");
+        if (!pl.copy()) {
+            std::vector<float> h, dev;
+            resample_taps(o.rate[b], pl, h);
+            resample_taps_device(pl, h, dev);
+            if ((rc = put_in(tabs[b], dev.data(), 1, (long)dev.size(), 4, 0, 0xFF))) return rc;
+        }
+        clips[b] = ResampleClip{o.in_off[b], o.out_off[b] + (long)G * (2 * b + 1), o.n_in[b], o.n_out[b], pl.L, pl.M, pl.H,
+                                tabs[b].ptr<float>()};
+        for (long f = 0; f < o.n_out[b]; f += resample_tile()) blocks.push_back(make_int2(b, (int)f));
+    }
+    const long out_len = o.out_tot + 2L * G * B;
+    // the packed input with `guard` floats of 0xFF after it
+    KtBuf in, dclips, dblocks, out, out2;
+    in.bytes = (size_t)(o.in_tot + G) * 4 + 256;
+    HIPCHK(hipMalloc((void **)&in.d, in.bytes));
+    HIPCHK(hipMemset(in.d, 0xFF, in.bytes));
+    if (o.in_tot) HIPCHK(hipMemcpy(in.d, a->pcm, (size_t)o.in_tot * 4, hipMemcpyHostToDevice));
+    const int2 none = make_int2(0, 0);
+    if ((rc = put_state(dclips, clips.data(), clips.size() * sizeof(ResampleClip))) ||
+        (rc = put_state(dblocks, blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(int2))) ||
+        (rc = put_out(out, a->out, out_len, 1, 4, 0)) || (rc = put_out(out2, a->launches == 2 ? a->out2 : nullptr, out_len, 1, 4, 0)))
+        return rc;
+    const float *d_in = in.ptr<float>();
+    launch_resample(d_in, dclips.ptr<ResampleClip>(), dblocks.ptr<int2>(), (int)blocks.size(), out.ptr<float>(), nullptr);
+    if (a->launches == 2)
+        launch_resample(d_in, dclips.ptr<ResampleClip>(), dblocks.ptr<int2>(), (int)blocks.size(), out2.ptr<float>(), nullptr);
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipDeviceSynchronize();
+    if (le != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (se != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel run: ") + hipGetErrorString(se));
+    a->tile = resample_tile();
+    if ((rc = get(out, a->out)) || (rc = get(out2, a->out2))) return rc;
+    return 0;
+}

@@ -23,6 +23,23 @@ void launch_mel(const float *pcm, const MelClip *clips, int n_clips, const int2 
                 float *out, hipStream_t s);
 int mel_frames_per_block();
 
+// ---------------------------------------------------------------- resampler to 16 kHz
+// One entry per clip (csrc/resample_host.h states the rule).  taps is the clip's rate's table in the device layout
+// [2H + 1][L]: entry [k][r] = h[(r * M) % L][k], so output n reads column n % L and a wavefront's lanes, whose
+// outputs are consecutive, load consecutive floats.  L == M == 1 is the copy (taps unused).
+struct ResampleClip {
+    long in_off;    // first sample of the raw clip in the input buffer
+    long out_off;   // first sample of the resampled clip in the output buffer
+    int n_in, n_out;
+    int L, M, H;
+    const float *taps;
+};
+// blocks: (clip, first output of the tile), resample_tile() outputs a block
+void launch_resample(const float *in, const ResampleClip *clips, const int2 *blocks, int n_blocks, float *out, hipStream_t s);
+int resample_tile();
+// a plan the kernel's LDS window holds (every supported rate does; the engine checks it before a launch)
+bool resample_fits(int L, int M, int H);
+
 // ---------------------------------------------------------------- conv front-end
 // One entry per 100-frame mel chunk (src/audio_encoder.cpp:331-409).
 // conv2 / conv3 weight row length: 9 * channels rounded up to 128, zeros past 9 * channels

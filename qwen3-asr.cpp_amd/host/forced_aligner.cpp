@@ -101,6 +101,21 @@ alignment_result ForcedAligner::align(const std::string &audio_path, const std::
         result.error_msg = "Failed to load audio file: " + audio_path;
         return result;
     }
+    if (sr != 16000 && resample_) {   // to 16 kHz on the device, then the path of a 16 kHz file
+        const int n = (int)samples.size(), n16 = qasr_resample_len(n, sr);
+        if (n16 < 0 || !ensure_ctx(1)) {
+            result.error_msg = n16 < 0 ? std::string("Failed to resample audio: ") + qasr_last_error() : error_msg_;
+            return result;
+        }
+        std::vector<float> out(std::max(n16, 1));
+        const float *ptr = samples.data();
+        if (qasr_resample(ctx_, &ptr, &n, &sr, 1, out.data()) != 0) {
+            result.error_msg = std::string("Failed to resample audio: ") + qasr_last_error();
+            return result;
+        }
+        out.resize(n16);
+        return align(out.data(), n16, text, language);
+    }
     if (sr != 16000) {
         result.error_msg = "Audio must be 16kHz, got " + std::to_string(sr) + " Hz";
         return result;

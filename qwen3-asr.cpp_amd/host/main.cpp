@@ -34,6 +34,7 @@ struct cli_params {
     int32_t max_tokens = 1024, n_threads = 4, device = 0, batch = 16;
     std::vector<int> devices;   // --devices: shard the files over these GPUs
     bool print_progress = false, print_timing = true, print_tokens = false, profile = false;
+    bool resample = false;   // --resample: files at other rates go through the device resampler
     bool logprobs = false;   // --logprobs: per-token log-probabilities (transcribe_params::token_logprobs)
     int32_t top_k = 0;       // --top-k: alternatives per token (transcribe_params::top_k)
     int32_t beam_width = 0;  // --beam-width: beam search of this width (transcribe_params::beam_width)
@@ -64,6 +65,8 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --max-tokens <n>       Maximum tokens to generate (default: 1024)\n");
     fprintf(stderr, "  --progress             Print progress during transcription\n");
     fprintf(stderr, "  --no-timing            Don't print timing information\n");
+    fprintf(stderr, "  --resample             Accept WAV files at 8 / 11.025 / 12 / 22.05 / 24 / 32 / 44.1 / 48 / 88.2 / 96 / 176.4 / 192 kHz:\n");
+    fprintf(stderr, "                         resampled to 16 kHz on the GPU (transcription, --align, --transcribe-align, --file-list, --devices)\n");
     fprintf(stderr, "  --tokens               Print token IDs\n");
     fprintf(stderr, "  --logprobs             Per-token log-probabilities: avg / min per file, and with --tokens each token's\n");
     fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
@@ -141,6 +144,7 @@ static bool parse(int argc, char **argv, cli_params &p) {
         else if (!strcmp(a, "--synthetic")) { if (!val(p.synthetic)) return false; }
         else if (!strcmp(a, "--progress")) p.print_progress = true;
         else if (!strcmp(a, "--no-timing")) p.print_timing = false;
+        else if (!strcmp(a, "--resample")) p.resample = true;
         else if (!strcmp(a, "--tokens")) p.print_tokens = true;
         else if (!strcmp(a, "--logprobs")) p.logprobs = true;
         else if (!strcmp(a, "--top-k")) {
@@ -388,6 +392,7 @@ static int run_alignment(const cli_params &p) {
     fprintf(stderr, "\n");
     qwen3_asr::ForcedAligner al;
     if (!load_aligner(al, p.model_path, p.language, p.device)) return 1;
+    al.set_resample(p.resample);
     fprintf(stderr, "Model loaded. Running alignment...\n");
     auto r = al.align(p.audio_paths[0], p.align_text, p.language);
     if (!r.success) { fprintf(stderr, "Error: %s\n", r.error_msg.c_str()); return 1; }
@@ -415,6 +420,7 @@ static int run_transcribe_and_align(const cli_params &p) {
     tp.n_threads = p.n_threads;
     tp.print_progress = p.print_progress;
     tp.print_timing = p.print_timing;
+    tp.resample = p.resample;
     auto ar = asr.transcribe(p.audio_paths[0], tp);
     if (!ar.success) { fprintf(stderr, "Error (ASR): %s\n", ar.error_msg.c_str()); return 1; }
     const std::string detected = detect_language(ar.text);
@@ -427,6 +433,7 @@ static int run_transcribe_and_align(const cli_params &p) {
     fprintf(stderr, "\n--- Phase 2: Forced Alignment ---\n");
     qwen3_asr::ForcedAligner al;
     if (!load_aligner(al, p.aligner_model_path, lang, p.device)) return 1;
+    al.set_resample(p.resample);
     auto r = al.align(p.audio_paths[0], transcript, lang);
     if (!r.success) { fprintf(stderr, "Error (Aligner): %s\n", r.error_msg.c_str()); return 1; }
     if (p.print_timing) {
@@ -437,6 +444,18 @@ static int run_transcribe_and_align(const cli_params &p) {
         fprintf(stderr, "  Words aligned: %zu\n", r.words.size());
     }
     return write_output(p, alignment_to_json(r) + "\n");
+}
+
+// the sample rate a WAV file's header states (fmt chunk first, as write_wav and most encoders lay it out); 16000
+// where the file cannot be read that way -- only an estimate of the clip's length hangs on it
+static int wav_header_rate(const std::string &path) {
+    unsigned char h[28];
+    FILE *f = fopen(path.c_str(), "rb");
+    const size_t k = f ? fread(h, 1, sizeof h, f) : 0;
+    if (f) fclose(f);
+    if (k < sizeof h || memcmp(h, "RIFF", 4) || memcmp(h + 8, "WAVE", 4) || memcmp(h + 12, "fmt ", 4)) return 16000;
+    const int sr = h[24] | h[25] << 8 | h[26] << 16 | h[27] << 24;
+    return sr > 0 ? sr : 16000;
 }
 
 // --devices: one host thread per GPU, each with its own model replica and
@@ -451,6 +470,8 @@ static int run_transcription_sharded(const cli_params &p) {
     for (size_t i = 0; i < N; i++) {
         struct stat st;
         size[i] = stat(p.audio_paths[i].c_str(), &st) == 0 ? (long long)st.st_size : 0;
+        // --resample: the queue order, the stream's cap and its context go by the samples at 16 kHz
+        if (p.resample) size[i] = size[i] * 16000 / wav_header_rate(p.audio_paths[i]);
     }
     std::vector<size_t> order(N);
     for (size_t i = 0; i < N; i++) order[i] = i;
@@ -491,14 +512,15 @@ static int run_transcription_sharded(const cli_params &p) {
             tp.max_tokens = p.max_tokens;
             tp.language = p.language;
             tp.print_timing = false;
-            auto fetch = [&](int &id, std::vector<float> &pcm) {
+            tp.resample = p.resample;
+            auto fetch = [&](int &id, std::vector<float> &pcm, int &sr) {
                 for (;;) {
                     const size_t k = next++;
                     if (k >= NS) return false;
                     const size_t i = order[k];
-                    int sr = 0;
-                    if (qwen3_asr::load_audio_file(p.audio_paths[i], pcm, sr) && sr == 16000) {
-                        samples += (long long)pcm.size();
+                    sr = 0;
+                    if (qwen3_asr::load_audio_file(p.audio_paths[i], pcm, sr) && (sr == 16000 || (p.resample && sr > 0))) {
+                        samples += (long long)pcm.size() * 16000 / sr;
                         id = (int)i;
                         return true;
                     }
@@ -510,7 +532,7 @@ static int run_transcription_sharded(const cli_params &p) {
                 std::lock_guard<std::mutex> lk(res_mu);
                 results[id] = std::move(r);
             };
-            if (NS && !asr.transcribe_stream(fetch, sink, tp, n_ctx)) { errors[g] = asr.get_error(); return; }
+            if (NS && !asr.transcribe_stream_rate(fetch, sink, tp, n_ctx)) { errors[g] = asr.get_error(); return; }
             for (size_t k; (k = next_long++) < longq.size();) {   // files past the stream's cap, one at a time
                 const size_t i = longq[k];
                 qwen3_asr::transcribe_result r = asr.transcribe(p.audio_paths[i], tp);
@@ -564,19 +586,22 @@ static int run_transcription(const cli_params &p) {
     tp.hotwords = p.hotwords;
     tp.hotword_boost = p.hotword_boost;
     tp.hotword_boosts = p.hotword_boosts;
+    tp.resample = p.resample;
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));
     } else {
         std::vector<std::vector<float>> clips;
+        std::vector<int> rates;
         for (auto &a : p.audio_paths) {
             std::vector<float> s;
             int sr = 0;
-            if (!qwen3_asr::load_audio_file(a, s, sr) || sr != 16000) { fprintf(stderr, "Error: bad audio %s\n", a.c_str()); return 1; }
+            if (!qwen3_asr::load_audio_file(a, s, sr) || (sr != 16000 && !p.resample)) { fprintf(stderr, "Error: bad audio %s\n", a.c_str()); return 1; }
             clips.push_back(std::move(s));
+            rates.push_back(sr);
         }
         asr.set_max_batch(p.batch);
-        results = asr.transcribe_batch(clips, tp);
+        results = p.resample ? asr.transcribe_batch(clips, rates, tp) : asr.transcribe_batch(clips, tp);
     }
     std::string all;
     for (size_t f = 0; f < results.size(); f++) {

@@ -204,11 +204,19 @@ transcribe_result Qwen3ASR::transcribe(const std::string &audio_path, const tran
         result.error_msg = "Failed to load audio file: " + audio_path;
         return result;
     }
+    if (sr != 16000 && params.resample) return transcribe(samples.data(), (int)samples.size(), sr, params);
     if (sr != 16000) {
         result.error_msg = "Audio must be 16kHz, got " + std::to_string(sr) + " Hz";
         return result;
     }
     return transcribe_internal(samples.data(), (int)samples.size(), params);
+}
+
+// samples at sample_rate: transcribe_internal with the resampler in front
+transcribe_result Qwen3ASR::transcribe(const float *samples, int n_samples, int sample_rate, const transcribe_params &params) {
+    transcribe_result result;
+    if (!model_) { result.error_msg = "Model not loaded"; return result; }
+    return transcribe_internal(samples, n_samples, params, sample_rate);
 }
 
 transcribe_result Qwen3ASR::transcribe(const float *samples, int n_samples, const transcribe_params &params) {
@@ -219,8 +227,9 @@ transcribe_result Qwen3ASR::transcribe(const float *samples, int n_samples, cons
 
 // one clip through qasr_run: the stage timings and --profile sections of the
 // reference's transcribe_internal (src/qwen3_asr.cpp:81-160)
+// rates: the clips' sample rates (null: 16 kHz), resampled on the device before the mel stage
 std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::vector<float>> &clips,
-                                                        const transcribe_params &params) {
+                                                        const transcribe_params &params, const std::vector<int> *rates) {
     const int B = (int)clips.size();
     std::vector<transcribe_result> out(B);
     if (!model_) { for (auto &r : out) r.error_msg = "Model not loaded"; return out; }
@@ -230,7 +239,12 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     for (int b = 0; b < B; b++) {
         ptr[b] = clips[b].data();
         n[b] = (int)clips[b].size();
-        maxP = std::max(maxP, qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(n[b]))));
+        int n16 = n[b];   // the prompt comes from the samples at 16 kHz
+        if (rates && (n16 = qasr_resample_len(n[b], (*rates)[b])) < 0) {
+            for (auto &r : out) r.error_msg = std::string("Failed to resample audio: ") + qasr_last_error();
+            return out;
+        }
+        maxP = std::max(maxP, qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(n16))));
     }
     const int64_t t0 = now_ms();
     std::vector<int32_t> sys;
@@ -259,7 +273,8 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
     TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
     const bool per_token = !beam && !many && (progress_callback_ || params.print_progress);
     qasr_set_token_callback(ctx_, per_token ? token_cb : nullptr, per_token ? &tcb : nullptr);
-    const int rc = qasr_transcribe_batch(ctx_, ptr.data(), n.data(), B, params.max_tokens, 0, toks.data(), nt.data(), &tm);
+    const int rc = rates ? qasr_transcribe_batch_rate(ctx_, ptr.data(), n.data(), rates->data(), B, params.max_tokens, 0, toks.data(), nt.data(), &tm)
+                         : qasr_transcribe_batch(ctx_, ptr.data(), n.data(), B, params.max_tokens, 0, toks.data(), nt.data(), &tm);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
     if (rc != 0) {
         for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
@@ -361,31 +376,49 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
 // reference's per-call error strings
 std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std::vector<float>> &clips,
                                                           const transcribe_params &params) {
-    if (clips.size() <= 1) return transcribe_run(clips, params);
+    return batch_impl(clips, nullptr, params);
+}
+
+std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std::vector<float>> &clips, const std::vector<int> &rates,
+                                                          const transcribe_params &params) {
+    if (rates.size() != clips.size())
+        return std::vector<transcribe_result>(clips.size(), [] { transcribe_result r; r.error_msg = "One sample rate per clip"; return r; }());
+    return batch_impl(clips, &rates, params);
+}
+
+std::vector<transcribe_result> Qwen3ASR::batch_impl(const std::vector<std::vector<float>> &clips, const std::vector<int> *rates,
+                                                    const transcribe_params &params) {
+    if (clips.size() <= 1) return transcribe_run(clips, params, rates);
     // the stream has neither beam search, sampling nor decoding constraints: whole runs of as many clips as max_batch() rows hold
     if (params.beam_width >= 2 || params.temperature > 0.f || constraints_asked(params)) {
         std::vector<transcribe_result> out;
         const size_t per = (size_t)std::max(1, max_batch_ / std::max(1, params.beam_width >= 2 ? params.beam_width : params.n_best));
         for (size_t i = 0; i < clips.size(); i += per) {
             std::vector<std::vector<float>> part(clips.begin() + i, clips.begin() + std::min(clips.size(), i + per));
-            for (auto &r : transcribe_run(part, params)) out.push_back(std::move(r));
+            std::vector<int> prates;
+            if (rates) prates.assign(rates->begin() + i, rates->begin() + std::min(clips.size(), i + per));
+            for (auto &r : transcribe_run(part, params, rates ? &prates : nullptr)) out.push_back(std::move(r));
         }
         return out;
     }
     if (!model_) return std::vector<transcribe_result>(clips.size(), [] { transcribe_result r; r.error_msg = "Model not loaded"; return r; }());
     std::vector<transcribe_result> out(clips.size());
     int maxP = 0;
-    for (const auto &c : clips) maxP = std::max(maxP, qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames((int)c.size()))));
+    for (size_t i = 0; i < clips.size(); i++) {   // (a clip at an unsupported rate fails alone in the stream: it sizes nothing)
+        const int n16 = rates ? qasr_resample_len((int)clips[i].size(), (*rates)[i]) : (int)clips[i].size();
+        maxP = std::max(maxP, qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(std::max(n16, 0)))));
+    }
     const int n_sys = params.system_prompt.empty() ? 0 : std::max(qasr_tokenize(model_, params.system_prompt.c_str(), nullptr, 0), 0);
     size_t next = 0;
-    const bool ok = transcribe_stream(
-        [&](int &id, std::vector<float> &pcm) {
+    const bool ok = stream_impl(
+        [&](int &id, std::vector<float> &pcm, int &rate) {
             if (next >= clips.size()) return false;
             id = (int)next;
+            if (rates) rate = (*rates)[next];
             pcm = clips[next++];
             return true;
         },
-        [&](int id, transcribe_result r) { out[id] = std::move(r); }, params, maxP + n_sys + params.max_tokens,
+        rates != nullptr, [&](int id, transcribe_result r) { out[id] = std::move(r); }, params, maxP + n_sys + params.max_tokens,
         std::min((int)clips.size(), max_batch_));
     if (!ok)
         for (auto &r : out)
@@ -395,7 +428,7 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_batch(const std::vector<std:
 
 namespace {
 struct StreamCtx {
-    const std::function<bool(int &, std::vector<float> &)> *fetch;
+    const std::function<bool(int &, std::vector<float> &, int &)> *fetch;
     const std::function<void(int, transcribe_result)> *sink;
     qasr_model *model;
     std::vector<float> pcm;
@@ -404,14 +437,16 @@ struct StreamCtx {
     qasr_ctx *tk_ctx;   // non-null: transcribe_params::top_k, its value in top_k
     int top_k;
 };
-int stream_fetch(void *u, const float **pcm, int *n, int *) {
+int stream_fetch_rate(void *u, const float **pcm, int *n, int *rate, int *) {
     StreamCtx *s = (StreamCtx *)u;
-    int id = -1;
-    if (!(*s->fetch)(id, s->pcm) || id < 0) return -1;
+    int id = -1, sr = 16000;
+    if (!(*s->fetch)(id, s->pcm, sr) || id < 0) return -1;
     *pcm = s->pcm.data();
     *n = (int)s->pcm.size();
+    if (rate) *rate = sr;
     return id;
 }
+int stream_fetch(void *u, const float **pcm, int *n, int *budget) { return stream_fetch_rate(u, pcm, n, nullptr, budget); }
 void stream_sink(void *u, int id, int status, const int32_t *toks, int n) {
     StreamCtx *s = (StreamCtx *)u;
     transcribe_result r;
@@ -446,6 +481,19 @@ void stream_sink(void *u, int id, int status, const int32_t *toks, int n) {
 bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<float> &pcm)> &fetch,
                                  const std::function<void(int id, transcribe_result result)> &sink,
                                  const transcribe_params &params, int n_ctx, int slots) {
+    return stream_impl([&](int &id, std::vector<float> &pcm, int &) { return fetch(id, pcm); }, false, sink, params, n_ctx, slots);
+}
+
+bool Qwen3ASR::transcribe_stream_rate(const std::function<bool(int &id, std::vector<float> &pcm, int &rate)> &fetch,
+                                      const std::function<void(int id, transcribe_result result)> &sink,
+                                      const transcribe_params &params, int n_ctx, int slots) {
+    return stream_impl(fetch, true, sink, params, n_ctx, slots);
+}
+
+// with_rates: the fetch's rate is honoured (qasr_run_stream_rate); else every clip is 16 kHz PCM (qasr_run_stream)
+bool Qwen3ASR::stream_impl(const std::function<bool(int &id, std::vector<float> &pcm, int &rate)> &fetch, bool with_rates,
+                           const std::function<void(int id, transcribe_result result)> &sink, const transcribe_params &params,
+                           int n_ctx, int slots) {
     if (!model_) { error_msg_ = "Model not loaded"; return false; }
     std::vector<int32_t> sys;
     if (!params.system_prompt.empty()) {
@@ -470,7 +518,8 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     qasr_set_token_callback(ctx_, per_token ? stream_token_cb : nullptr, per_token ? &tcb : nullptr);
     StreamCtx sc{&fetch, &sink, model_, {}, now_ms(), params.token_logprobs ? ctx_ : nullptr,
                  params.top_k > 0 ? ctx_ : nullptr, params.top_k};
-    const int rc = qasr_run_stream(ctx_, S, stream_fetch, stream_sink, &sc, params.max_tokens, 0, nullptr);
+    const int rc = with_rates ? qasr_run_stream_rate(ctx_, S, stream_fetch_rate, stream_sink, &sc, params.max_tokens, 0, nullptr)
+                              : qasr_run_stream(ctx_, S, stream_fetch, stream_sink, &sc, params.max_tokens, 0, nullptr);
     qasr_set_token_callback(ctx_, nullptr, nullptr);
     if (rc != 0) { error_msg_ = std::string("Decoding failed: ") + qasr_last_error(); return false; }
     if (profile_) {
@@ -483,9 +532,11 @@ bool Qwen3ASR::transcribe_stream(const std::function<bool(int &id, std::vector<f
     return true;
 }
 
-transcribe_result Qwen3ASR::transcribe_internal(const float *samples, int n_samples, const transcribe_params &params) {
+// sample_rate 0: 16 kHz PCM; else the resampler in front (qasr_transcribe_batch_rate)
+transcribe_result Qwen3ASR::transcribe_internal(const float *samples, int n_samples, const transcribe_params &params, int sample_rate) {
     std::vector<std::vector<float>> one(1, std::vector<float>(samples, samples + n_samples));
-    transcribe_result r = transcribe_run(one, params)[0];
+    const std::vector<int> rate(1, sample_rate);
+    transcribe_result r = transcribe_run(one, params, sample_rate ? &rate : nullptr)[0];
     if (r.success && params.print_timing) {
         fprintf(stderr, "\nTiming:\n");
         fprintf(stderr, "  Mel spectrogram: %lld ms\n", (long long)r.t_mel_ms);

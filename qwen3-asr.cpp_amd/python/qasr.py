@@ -41,6 +41,8 @@ EXPORTS = [
     "qasr_set_sampling", "qasr_get_sampling", "qasr_set_sample_streams", "qasr_get_samples",
     "qasr_constraints_validate", "qasr_set_constraints", "qasr_get_constraints",
     "qasr_phrases_validate", "qasr_set_phrases", "qasr_get_phrases", "qasr_phrase_tokenize",
+    "qasr_resample_plan", "qasr_resample_len", "qasr_resample_taps", "qasr_resample_host",
+    "qasr_resample", "qasr_resample_last_us", "qasr_stage_audio_rate", "qasr_transcribe_batch_rate", "qasr_run_stream_rate",
 ]
 
 
@@ -93,6 +95,9 @@ _lib = None
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int32)
 # int (*)(void *user, const float **pcm, int *n_samples, int *max_tokens)
 FETCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(C.c_int))
+# int (*)(void *user, const float **pcm, int *n_samples, int *rate, int *max_tokens)
+FETCH_RATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                            C.POINTER(C.c_int))
 # int (*)(void *user, int *max_tokens)
 FETCH_STAGED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int))
 # void (*)(void *user, int id, int status, const int32_t *tokens, int n_tokens)
@@ -160,6 +165,13 @@ def lib() -> C.CDLL:
             "qasr_set_phrases": ([P, C.POINTER(Phrases)], I),
             "qasr_get_phrases": ([P, C.POINTER(Phrases), I32P, I32P, F, I, I], I),
             "qasr_phrase_tokenize": ([P, C.c_char_p, I32P, I32P, I], I),
+            "qasr_resample_plan": ([I, IP, IP, IP], I), "qasr_resample_len": ([I, I], I),
+            "qasr_resample_taps": ([I, F, I], I), "qasr_resample_host": ([F, I, I, F], I),
+            "qasr_resample": ([P, C.POINTER(F), IP, IP, I, F], I),
+            "qasr_resample_last_us": ([P], I),
+            "qasr_stage_audio_rate": ([P, C.POINTER(F), IP, IP, I], I),
+            "qasr_transcribe_batch_rate": ([P, C.POINTER(F), IP, IP, I, I, I, I32P, IP, C.POINTER(Timings)], I),
+            "qasr_run_stream_rate": ([P, I, FETCH_RATE_FN, SINK_FN, P, I, I, C.POINTER(StreamStats)], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -290,6 +302,41 @@ def load_wav(path: str):
 def write_wav(path: str, pcm: np.ndarray, sr: int = 16000) -> None:
     pcm = np.ascontiguousarray(pcm, np.float32)
     _check(lib().qasr_write_wav(path.encode(), _f(pcm), len(pcm), sr), "write_wav")
+
+
+# ---- the resampler to 16 kHz (host only) ----
+def _neg(rc: int, what: str) -> int:
+    if rc < 0:
+        raise QasrError(f"{what}: {lib().qasr_last_error().decode(errors='replace')}")
+    return rc
+
+
+def resample_plan(rate: int) -> Tuple[int, int, int]:
+    """(L, M, H) of a rate: 16000 / gcd, rate / gcd, taps a side; raises QasrError for an unsupported rate"""
+    L, M, H = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().qasr_resample_plan(int(rate), C.byref(L), C.byref(M), C.byref(H)), "qasr_resample_plan")
+    return L.value, M.value, H.value
+
+
+def resample_len(n_in: int, rate: int) -> int:
+    """samples at 16 kHz of n_in samples at `rate`"""
+    return _neg(lib().qasr_resample_len(int(n_in), int(rate)), "qasr_resample_len")
+
+
+def resample_taps(rate: int) -> np.ndarray:
+    """the tap table h[L][2H + 1] of a rate (fp32)"""
+    L, _M, H = resample_plan(rate)
+    out = np.zeros((L, 2 * H + 1), np.float32)
+    _neg(lib().qasr_resample_taps(int(rate), _f(out), out.size), "qasr_resample_taps")
+    return out
+
+
+def resample_host(pcm: np.ndarray, rate: int) -> np.ndarray:
+    """the rule on the CPU (qasr_resample_host): the reference of the device resampler"""
+    pcm = np.ascontiguousarray(pcm, np.float32)
+    out = np.zeros(max(resample_len(len(pcm), rate), 1), np.float32)
+    n = _neg(lib().qasr_resample_host(_f(pcm), len(pcm), int(rate), _f(out)), "qasr_resample_host")
+    return out[:n]
 
 
 def fix_timestamps(classes: Sequence[int]) -> List[int]:
@@ -516,6 +563,27 @@ class Context:
             res.append(out[o:o + 128 * t].reshape(128, t))
             o += 128 * t
         return res
+
+    def resample(self, clips: Sequence[np.ndarray], rates: Sequence[int]) -> List[np.ndarray]:
+        """qasr_resample: clips at `rates` -> the clips at 16 kHz, resampled on the device"""
+        clips = [np.ascontiguousarray(c, np.float32) for c in clips]
+        n = np.array([len(c) for c in clips], np.int32)
+        r = np.ascontiguousarray(rates, np.int32)
+        if len(r) != len(clips):
+            raise QasrError("resample: one rate per clip")
+        no = [resample_len(int(k), int(q)) for k, q in zip(n, r)]
+        out = np.zeros(max(1, sum(no)), np.float32)
+        ptrs = (C.POINTER(C.c_float) * len(clips))(*[_f(c) for c in clips])
+        _check(lib().qasr_resample(self.h, ptrs, _i(n), _i(r), len(clips), _f(out)), "qasr_resample")
+        res, o = [], 0
+        for k in no:
+            res.append(out[o:o + k].copy())
+            o += k
+        return res
+
+    def resample_last_us(self) -> int:
+        """device time of the last resample() call's kernel launch, microseconds"""
+        return _neg(lib().qasr_resample_last_us(self.h), "qasr_resample_last_us")
 
     def _encode(self, mels: Sequence[np.ndarray], conv_only: bool, no_chunk: bool = False) -> List[np.ndarray]:
         T = np.array([m.shape[1] for m in mels], np.int32)
@@ -747,10 +815,18 @@ class Context:
         return logits, am
 
     # ---- whole path --------------------------------------------------------
-    def stage_audio(self, clips: Sequence[np.ndarray]) -> None:
+    def stage_audio(self, clips: Sequence[np.ndarray], rates: Optional[Sequence[int]] = None) -> None:
+        """rates: the clips' sample rates (qasr_stage_audio_rate resamples them to 16 kHz on the device);
+        None: every clip is 16 kHz PCM"""
         self._staged = [np.ascontiguousarray(c, np.float32) for c in clips]
         n = np.array([len(c) for c in self._staged], np.int32)
         ptrs = (C.POINTER(C.c_float) * len(self._staged))(*[_f(c) for c in self._staged])
+        if rates is not None:
+            r = np.ascontiguousarray(rates, np.int32)
+            if len(r) != len(self._staged):
+                raise QasrError("stage_audio: one rate per clip")
+            _check(lib().qasr_stage_audio_rate(self.h, ptrs, _i(n), _i(r), len(self._staged)), "qasr_stage_audio_rate")
+            return
         _check(lib().qasr_stage_audio(self.h, ptrs, _i(n), len(self._staged)), "qasr_stage_audio")
 
     def run(self, max_tokens: int, ignore_eos: bool = False) -> RunResult:
@@ -807,15 +883,30 @@ class Context:
         return self._run_result(toks, nt, t, max_tokens)
 
     def run_stream(self, next_clip, max_tokens: int, ignore_eos: bool = False, slots: int = 0, logprobs: bool = False,
-                   topk: bool = False):
+                   topk: bool = False, with_rates: bool = False):
         """Continuous batching (qasr_run_stream): next_clip() -> (id, pcm[, budget])
         or None when the queue is empty; returns ({id: tokens | QasrError},
         StreamStats).  Slots (0: max_batch) freed by a finished clip are
         refilled at the next chunk boundary; a clip that fails alone maps to
         its QasrError.  logprobs=True (option token_logprobs on): a clip maps
         to (tokens, logprobs) instead.  topk=True (option top_k on) appends
-        (ids [n][K], logprobs [n][K]) to that tuple."""
+        (ids [n][K], logprobs [n][K]) to that tuple.  with_rates=True
+        (qasr_run_stream_rate): next_clip() -> (id, pcm, rate[, budget]), the
+        clip resampled to 16 kHz on the device when its slot is refilled."""
         out, keep = {}, []
+
+        def fetch_rate(_u, pcm_pp, n_p, rate_p, budget_p):
+            item = next_clip()
+            if item is None:
+                return -1
+            cid, pcm = int(item[0]), np.ascontiguousarray(item[1], np.float32)
+            keep[:] = [pcm]
+            pcm_pp[0] = _f(pcm)
+            n_p[0] = len(pcm)
+            rate_p[0] = int(item[2])
+            if len(item) > 3:
+                budget_p[0] = int(item[3])
+            return cid
 
         def fetch(_u, pcm_pp, n_p, budget_p):
             item = next_clip()
@@ -830,10 +921,10 @@ class Context:
             return cid
 
         failed = []
-        f, k = FETCH_FN(_guarded_fetch(fetch, failed)), SINK_FN(_sink_into(out, failed, self if logprobs else None,
-                                                                                     self if topk else None))
+        f = FETCH_RATE_FN(_guarded_fetch(fetch_rate, failed)) if with_rates else FETCH_FN(_guarded_fetch(fetch, failed))
+        k = SINK_FN(_sink_into(out, failed, self if logprobs else None, self if topk else None))
         st = StreamStats()
-        rc = lib().qasr_run_stream(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
+        rc = (lib().qasr_run_stream_rate if with_rates else lib().qasr_run_stream)(self.h, int(slots), f, k, None, int(max_tokens), int(ignore_eos), C.byref(st))
         if failed:
             raise failed[0]
         _check(rc, "qasr_run_stream")
@@ -963,6 +1054,6 @@ class Context:
             lib().qasr_align_json_batch(self.h, ptrs, _i(n), tx, B, language.encode(), buf, k + 1, C.byref(t))
         return json.loads(buf.raw[:k].decode("utf-8")), t
 
-    def transcribe(self, clips, max_tokens=1024, ignore_eos=False) -> RunResult:
-        self.stage_audio(clips)
+    def transcribe(self, clips, max_tokens=1024, ignore_eos=False, rates=None) -> RunResult:
+        self.stage_audio(clips, rates)
         return self.run(max_tokens, ignore_eos)
