@@ -262,6 +262,9 @@ int qasr_run_stream_staged(qasr_ctx *c, int slots, qasr_fetch_staged_fn fetch, q
  *   "fuse_ffn" [QASR_FUSE_FFN], "fuse_qkv" [QASR_FUSE_QKV], "fuse_o" [QASR_FUSE_O]
  *       1/0: the fused launch or the separate launches (same arithmetic)
  *   "ffn_delay", "ffn_wdelay", "qkv_delay", "o_delay"  in-launch delays (~0.2 us units)
+ *   "kvw_delay" [QASR_KVW_DELAY], "k_stagger" [QASR_K_STAGGER], "vt_stagger" [QASR_VT_STAGGER]
+ *       the QKV + attention launch's memory requests in the order the attention chain
+ *       needs them (same units; 0: every request at its role's start)
  *   "att_spl1" [QASR_ATT_SPL1]   batch <= 8 attention key split: 0 auto, 64, 128
  *   "poll_limit" [QASR_POLL_LIMIT]  bounded in-launch waits (polls); a wait that
  *       runs out makes the call fail with QASR_ERR_DEVICE

@@ -703,8 +703,11 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs a, const i
     if constexpr (!FUSED) { x0 = src[lane]; x1 = src[lane + 64]; }
     const float *nw = wid < 2 ? a.q_norm : a.k_norm;
     const float w0 = nw[lane], w1 = nw[lane + 64];
-    if constexpr (FUSED)   // let the QKV blocks' weight stream get ahead in the memory queues
-        for (int i = 0; i < a.fuse_delay; i++) __builtin_amdgcn_s_sleep(8);
+    if constexpr (FUSED) {   // let the QKV blocks' weight stream get ahead in the memory queues; the splits
+        // of the chain's later 256-key chunks k_stagger a chunk behind those of its first
+        const int nd = a.fuse_delay + (sp * SPL / 256) * a.k_stagger;
+        for (int i = 0; i < nd; i++) __builtin_amdgcn_s_sleep(8);
+    }
     // ---- every K/V row of the split (addresses depend on blockIdx only).  Decode
     //      rows are cache slots: row b of a decode step is slot b (qasr_run_stream
     //      refills a finished slot in place, its prefill writing through seq_slot
@@ -756,20 +759,27 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs a, const i
         // (sc1 loads) until both carry this step's tag -- the data arrives with
         // its own flag, no drain / arrival count / second load (MI355X guide,
         // hand-off table: data-tagged granules).  Bounded like the counter wait.
-        const uint32_t tag = gran_tag(a.pos[b], a.layer);
-        const unsigned long long *gp = a.gran + (src - raw) + lane;
-        unsigned long long v0 = 0, v1 = 0;
-        bool ok = false;
-        for (int it = 0; it < a.poll_limit; it++) {
-            v0 = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v1 = __hip_atomic_load(gp + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = (uint32_t)(v0 >> 32) == tag && (uint32_t)(v1 >> 32) == tag;
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(2);
+        // The new token's k and v are used by the last split alone (knew / vnew,
+        // the cache rows): in every other split waves 2 and 3 go straight to the
+        // barrier (x = 0, nothing stored), so the scores of the keys before the
+        // new one wait for the q rows of the QKV role and not for its k and v rows.
+        const int gpos = a.pos[b];
+        const uint32_t tag = gran_tag(gpos, a.layer);
+        if (wid < 2 || sp == gpos / SPL) {
+            const unsigned long long *gp = a.gran + (src - raw) + lane;
+            unsigned long long v0 = 0, v1 = 0;
+            bool ok = false;
+            for (int it = 0; it < a.poll_limit; it++) {
+                v0 = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                v1 = __hip_atomic_load(gp + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok = (uint32_t)(v0 >> 32) == tag && (uint32_t)(v1 >> 32) == tag;
+                if (__all(ok)) break;
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (!__all(ok) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_QKV_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            x0 = __uint_as_float((uint32_t)v0);
+            x1 = __uint_as_float((uint32_t)v1);
         }
-        if (!__all(ok) && lane == 0) __hip_atomic_fetch_or(a.err, (unsigned)DEVERR_QKV_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x0 = __uint_as_float((uint32_t)v0);
-        x1 = __uint_as_float((uint32_t)v1);
     } else if constexpr (FUSED) {
         // wait for the kv group's 64 QKV workgroups (bounded: a lost arrival must
         // not hang the GPU), then read their write-through outputs with sc1 loads
@@ -1259,8 +1269,9 @@ int decode_stream_slots() {
 // ------------------------------------------------- batch 1: QKV + attention
 // One launch for the batch-1 QKV projection and the attention it feeds.
 // Blocks [0, 512): the QKV GEMV (gemv1_kernel's arithmetic, K = 1024, 2 rows
-// per wave, RMS norm / layer-0 embedding gather per wave), block q serving kv
-// group q / 64 (its 256 q rows, 128 k rows, 128 v rows); outputs are stored
+// per wave, RMS norm / layer-0 embedding gather per wave), 8 output rows a
+// block in output order (256 q-row blocks, then 128 k-row, then 128 v-row
+// blocks: what every split waits for goes first); outputs are stored
 // write-through (sc1), every wave drains, and one lane counts the block into
 // qcnt[group] (MI355X_MICROARCH.md hand-off table, row 1).  Blocks past 512:
 // the group's attention splits, which issue their K/V loads before waiting
@@ -1522,17 +1533,38 @@ __device__ __forceinline__ void fx1_chain_body(const DecodeAttnArgs &a, const in
     // one 64-key buffer ahead: ~40 cycles a key instead of ~12 (device trace,
     // layer 14).  (The kv group's other head pulls the same bytes from its
     // own CU: whichever comes second hits the L2.)
-    if (a.fx_vpf & 2) {
-        typedef __attribute__((address_space(3))) void lds_void_c;
-        typedef __attribute__((address_space(1))) void glb_void_c;
-        lds_void_c *dst = (lds_void_c *)C.vpf[wid];
-        for (int kb = wid >> 1; kb * 8 < n; kb += 2)
-            __builtin_amdgcn_global_load_lds((glb_void_c *)(vt + (long)kb * 1024 + loff), dst, 16, 0, 0);
-    }
+    // vt_stagger > 0: only the first chunk's pieces (FX_PC keys) go out here;
+    // the chain waves, idle until the first chunk's weights, send the rest
+    // vt_stagger behind the barrier (wave w: every later key block of its
+    // dimension half).  Measured slower at every value (one wave's ~176 pieces
+    // are three memory round trips and its chain starts behind them; DESIGN.md
+    // section 5): 0 by default.
+    typedef __attribute__((address_space(3))) void lds_void_c;
+    typedef __attribute__((address_space(1))) void glb_void_c;
+    lds_void_c *vdst = (lds_void_c *)C.vpf[wid];
+    const int npf = a.vt_stagger > 0 ? min(n, FX_PC) : n;
+    // fx_vpf bit 2: the kv group's two chain workgroups (heads 2 g and 2 g + 1,
+    // one XCD) pull half of the key blocks each instead of all of them twice.
+    // A wave has at most 64 loads in flight, so its 96 pieces at 1.5k keys took
+    // two memory round trips, and the barrier below -- which the producer
+    // waves' first poll stands behind -- drains them; 48 a wave take one.
+    const int vhalf = (a.fx_vpf & 4) ? 1 : 0;
+    if (a.fx_vpf & 2)
+        for (int kb = (wid >> 1) + 2 * hh * vhalf; kb * 8 < npf; kb += 2 + 2 * vhalf)
+            __builtin_amdgcn_global_load_lds((glb_void_c *)(vt + (long)kb * 1024 + loff), vdst, 16, 0, 0);
     __syncthreads();   // the progress words are zero; the last barrier before the hand-off's
     if (wid >= 2) {
         fx1_gather_weights(a, head, n, C, wid - 2, tr);
     } else {
+        if ((a.fx_vpf & 2) && npf < n) {
+            for (int i = 0; i < a.vt_stagger; i++) __builtin_amdgcn_s_sleep(8);
+            for (int kb = FX_PC / 8; kb * 8 < n; kb++)
+                __builtin_amdgcn_global_load_lds((glb_void_c *)(vt + (long)kb * 1024 + loff), vdst, 16, 0, 0);
+            // drained here, where the wave has nothing to do yet: with LDS-DMA
+            // pieces pending on entry the compiler puts a vmcnt(0) in front of
+            // every LDS read of the chain loop
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+        }
         const uint32_t tag = gran_tag(pos, a.layer);
         const int QD = a.n_head * 128, KD = a.n_kv_head * 128;
         const float *fsc = C.fsc;
@@ -1685,13 +1717,19 @@ __global__ __launch_bounds__(256) void qkv_attn1_kernel(GemvArgs q, DecodeAttnAr
         return;
     }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int grp = blockIdx.x >> 6, loc = blockIdx.x & 63;
     if (q.trace && threadIdx.x == 0) q.trace[blockIdx.x * 8] = rt_now();
-    const int QD = a.n_head * 128, KD = a.n_kv_head * 128;
-    // the block's 8 rows: q rows of heads 2g, 2g+1, then k, then v of group g
-    const int rbase = loc < 32 ? grp * 256 + loc * 8 : loc < 48 ? QD + grp * 128 + (loc - 32) * 8 : QD + KD + grp * 128 + (loc - 48) * 8;
-    const int row0 = rbase + wid * RPW;
-    const uint32_t gtag = a.gran ? gran_tag(a.pos[0], a.layer) : 0u;
+    // the block's 8 rows, in the order of the output: blocks 0-255 the q rows
+    // (32 a kv group), 256-383 the k rows, 384-511 the v rows (16 a group each).
+    // Every split's scores need q; the new k is needed by the last split alone
+    // and the new v by the chain's last key, so the q rows' half of the weight
+    // stream is dispatched first and the k / v blocks may hold their request
+    // back (kvw_delay).  grp: the kv group whose arrival counter the block
+    // counts into (counter hand-off)
+    const int qb = blockIdx.x;
+    const int grp = qb < 256 ? qb >> 5 : (qb & 127) >> 4;
+    const int row0 = qb * 8 + wid * RPW;
+    if (qb >= 256)
+        for (int i = 0; i < a.kvw_delay; i++) __builtin_amdgcn_s_sleep(8);
     half8 wv[RPW][NT];
 #pragma unroll
     for (int r = 0; r < RPW; r++)
@@ -1738,6 +1776,9 @@ __global__ __launch_bounds__(256) void qkv_attn1_kernel(GemvArgs q, DecodeAttnAr
 #pragma unroll
         for (int e = 0; e < 8; e++) xf[t][e] = (float)f2h(fmul_rn(fmul_rn(xf[t][e], scale), w[e]));
     }
+    // (the position is read here, behind the weight request: a test of a.gran
+    // around it put the load and its wait in front of the request)
+    const uint32_t gtag = gran_tag(a.pos[0], a.layer);
 #pragma unroll
     for (int r = 0; r < RPW; r++) {
         float acc = 0.f;
@@ -1814,6 +1855,9 @@ int launch_qkv_attention1(const GemvArgs &q, const DecodeAttnArgs &a, const Gemv
     ad.err = cfg.err;
     ad.grid_splits = ns;   // the kernel's split count
     ad.fx_vpf = cfg.fx_vpf;
+    ad.kvw_delay = max(cfg.kvw_delay, 0);
+    ad.k_stagger = max(cfg.k_stagger, 0);
+    ad.vt_stagger = max(cfg.vt_stagger, 0);
     if (!with_o2) ad.att_done = nullptr;
     const GemvArgs qa = q;
     const GemvArgs oa = with_o2 ? *o : GemvArgs{};

@@ -49,6 +49,9 @@ static const std::vector<FuseOption> &fuse_options() {
         {"gran", "QASR_GRAN", &FuseCfg::gran},
         {"fa_exact_decode", "QASR_FA_EXACT_DECODE", &FuseCfg::fa_exact_decode},
         {"fx_vpf", "QASR_FX_VPF", &FuseCfg::fx_vpf},
+        {"kvw_delay", "QASR_KVW_DELAY", &FuseCfg::kvw_delay},
+        {"k_stagger", "QASR_K_STAGGER", &FuseCfg::k_stagger},
+        {"vt_stagger", "QASR_VT_STAGGER", &FuseCfg::vt_stagger},
         {"att_stream", "QASR_ATT_STREAM", &FuseCfg::att_stream},
         {"skinny", "QASR_SKINNY", &FuseCfg::skinny},
         {"att_spl", "QASR_ATT_SPL", &FuseCfg::att_spl},

@@ -235,6 +235,17 @@ struct FuseCfg {
                                         // round 2, tools/experiments.sh delays: 20 -> 26, configs[1] decode 218.4 -> 212.4 ms;
                                         // round 4 with the fp16-V chain, tools/r4/sweep.sh on one box: ffn_wdelay 14 -> 16-18,
                                         // o_delay 26 -> 30-38, 64-key splits to 1.9k keys: 248 -> 263 RTFx)
+    // the fused QKV + attention launch's requests in the order the chain needs them (s_sleep(8) units; all 0 =
+    // every request at its role's start, behind qkv_delay / o_delay alone).  Swept on one box at the flagship shape
+    // (tools/sweep_qkv_order.sh, 3 timed steps a point, profiles/qkv_order/sweep.txt; ms a step, base 305.1-306.9):
+    // with fx_vpf 6, kvw_delay 0 / 1 / 2 / 3 at k_stagger 6: 301.6 / 300.3 / 299.7 / 297.5; k_stagger 4 .. 9 flat within
+    // 1 ms at every kvw_delay, 10: +2.5 .. 4 ms, 12: +18 ms, 16: +54 ms (the later chunks' scores then arrive behind the
+    // chain); qkv_delay 6 .. 12 and o_delay 28 .. 56 within 2 ms of 10 / 32, qkv_delay 0 .. 7 without the stagger +6 .. 9 ms;
+    // vt_stagger 1 / 4 / 8 / 16: +3 / +9 / +17 / +30 ms (fx_vpf 2): off
+    int kvw_delay = 3;                  // the k- and v-row QKV blocks idle this long before their weight request (q rows first)
+    int k_stagger = 6;                  // split sp requests its K rows qkv_delay + (sp * split / 256) * k_stagger in (chunk order)
+    int vt_stagger = 0;                 // chain workgroups: V^T of the first 256 keys pulled at once, the rest by the chain
+                                        // waves this long behind the role's barrier (0: all of it ahead of the barrier)
     int spl1 = 0;                       // batch-1 attention split: 0 = auto (64, or 128 from 1k keys)
     int poll_limit = 1 << 20;           // bounded waits: polls (s_sleep(4..8) apart) before giving up
     int fence = 0;                      // 1 = agent release before each arrival, acquire after each wait
@@ -244,8 +255,9 @@ struct FuseCfg {
     int fa_exact_prefill = 1;           // prefill attention with ggml's CPU FA numerics (fa_exact.hip)
     int fa_exact_decode = 1;            // decode attention likewise: 1 on (every model and batch; batch 1 f16 in the
                                         // fused launch's chain role), 0 off (fp32 V accumulation, split-K)
-    int fx_vpf = 2;                     // batch-1 fused exact attention: V^T pulled into L2 ahead of the chain
-                                        // (DecodeAttnArgs.fx_vpf bits)
+    int fx_vpf = 6;                     // batch-1 fused exact attention: V^T pulled into L2 ahead of the chain
+                                        // (DecodeAttnArgs.fx_vpf bits; 6: by the kv group's two chain workgroups, half
+                                        // each -- 2 -> 6 with the three options above at 0: 305.5 -> 303.1 ms a step)
     int slots_ffn = 0, slots_qkv64 = 0, slots_qkv128 = 0;   // co-resident workgroups on this device
     int att_stream = 1;                 // decode batches: one workgroup per (kv group, sequence) (decode_attn_seq_kernel)
     int skinny = 1;                     // decode batches: the weight-streaming skinny GEMMs (0 = tiled GEMMs)
@@ -425,7 +437,9 @@ struct DecodeAttnArgs {
     int fx;
     unsigned long long *sgran;           // row stride sgran_ld(max_ctx) (16-B aligned granule pairs)
     int fx_vpf;                          // bit 0: the splits pull their keys' V^T rows into their XCD's L2 for the
-                                         // chain; bit 1: the chain workgroups pull their own (LDS-DMA, while waiting)
+                                         // chain; bit 1: the chain workgroups pull their own (LDS-DMA, while waiting);
+                                         // bit 2 (with bit 1): a kv group's two chain workgroups pull half each
+    int kvw_delay, k_stagger, vt_stagger;   // fused launch: request order (FuseCfg, s_sleep(8) units)
 };
 // the decode attention with ggml's CPU flash-attention numerics (fa_exact.hip),
 // after launch_decode_attention in scores mode: per (query head, sequence) the

@@ -7,8 +7,12 @@ import numpy as np
 NAMES = ["qkv_gemv", "attention", "oproj_gemv", "gateup_gemv", "down_gemv"]
 
 
-def main(path):
+def main(path, interleaved=False):
+    """interleaved: the QKV role's blocks numbered by kv group (32 q, 16 k, 16 v
+    blocks a group: builds before the q-rows-first order) instead of 256 q-row,
+    128 k-row, 128 v-row blocks"""
     t = np.fromfile(path, dtype=np.uint64).reshape(6, 4096, 8).astype(np.int64)
+    raw0, raw1 = t[0].copy(), t[1].copy()
     # chain workgroups.  Pipelined role (one workgroup a query head): rows 4000 + c = [start, chain start,
     # first chunk published, last chunk published, chain done, published, S done, producer polls], 4040 + c =
     # shader clock at chain start / end, keys, new-maximum keys, slow groups, 4080 + c = the two chain waves'
@@ -67,10 +71,29 @@ def main(path):
             print(f"{NAMES[k]:12s} blocks {len(x):4d} start {us(st.min()):7.2f}..{us(st.max()):7.2f}  "
                   f"end {us(en.min()):7.2f}..{us(en.max()):7.2f}  block-dur med {np.median(en - st) / 100:5.2f}")
             e = en.max()
+        if k == 0 and len(x) == 512 and (raw0[:512, 1] > 0).all():   # the fused launch's QKV role: q, k and v row blocks
+            b = np.arange(512)
+            kind = np.where((b & 63) < 32, 0, np.where((b & 63) < 48, 1, 2)) if interleaved else np.where(b < 256, 0, np.where(b < 384, 1, 2))
+            print(f"{'':12s} " + "  ".join(f"{nm} blocks end {us(raw0[:512, 1][kind == i].min()):5.2f}..{us(raw0[:512, 1][kind == i].max()):5.2f}"
+                                           for i, nm in enumerate("qkv")))
+        if k == 1 and len(ch) and wide:
+            # the splits' "inputs ready" (mark 1: q -- in the last split k and v too -- normed and the K rows landed)
+            # and publish (mark 3) marks: the last split (the new key's), the others, and those of the first chunk
+            n = int(ck[ck[:, 1] > ck[:, 0], 2][0])
+            nsp = len(x) // 8
+            spl = 64 if nsp * 64 >= n else 128
+            rows = raw1[:nsp * 8]
+            sp = np.arange(nsp * 8) % nsp
+            for nm, sel in (("last split", sp == (n - 1) // spl), ("other splits", sp != (n - 1) // spl),
+                            ("first chunk", (sp * spl < 256) & (sp != (n - 1) // spl))):
+                r = rows[sel & (rows[:, 0] > 0)]
+                if len(r):
+                    print(f"{'':12s} {nm:12s} ({len(r):3d}): inputs ready {us(np.median(r[:, 1])):5.2f}/{us(r[:, 1].max()):5.2f}  "
+                          f"published {us(np.median(r[:, 3])):5.2f}/{us(r[:, 3].max()):5.2f}  (median/max)")
         if prev_end is not None:
             print(f"{'':12s} gap from previous kernel's last block end to first start: {(st.min() - prev_end) / 100:5.2f} us")
         prev_end = e
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main([a for a in sys.argv[1:] if not a.startswith("--")][0], interleaved="--interleaved" in sys.argv)
