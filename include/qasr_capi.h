@@ -920,6 +920,85 @@ typedef struct {
 } qasr_kt_resample_args;
 int qasr_kt_resample(int device, qasr_kt_resample_args *a);
 
+/* ---- long recordings: pause segmentation into zero-copy pool clips --------
+ * A recording longer than one decoder context is uploaded once, cut on the device at its
+ * quietest points, and every piece becomes a pool entry that points into the recording: no PCM
+ * is copied and no clip is staged a second time.  The rule (csrc/segment_host.h states it in
+ * full), for a recording of n samples at 16 kHz, F = n / 160 frames:
+ *   e[f] = sum of the frame's 160 squared samples, fp64, ascending;
+ *   s[f] = sum of e over [max(0, f - H), min(F - 1, f + H)], fp64, ascending (H = smooth_half);
+ *   a = 0; while F - a > max_frames: the next cut is the frame of
+ *     [a + min_frames, min(a + max_frames, F - min_frames)] with the smallest s, equal values to
+ *     the LARGER frame; a = the cut;
+ *   segment k covers samples [160 cut_k, 160 cut_k+1), the last one ends at n; every recording has
+ *     at least one segment;
+ *   peak[k] = the maximum of s over the segment's frames (0 without frames), peak_rec the maximum
+ *     over the recording; with skip_ratio >= 0 segment k is silent iff
+ *     peak[k] <= skip_ratio * peak_rec; skip_ratio < 0: never silent.
+ * The device results equal the host rule exactly (cuts) and bit for bit (e, s, peaks) for finite
+ * input.  Ranges: 1 <= min_frames, 2 * min_frames <= max_frames <= 2^20, 0 <= smooth_half <= 64,
+ * skip_ratio not NaN; anything else is QASR_ERR_ARG with the range in qasr_last_error().
+ * Defaults: 3000, 1000, 5, -1.  params NULL: the defaults.
+ *
+ * host only (no device is touched):
+ *   qasr_segment_validate  0, or QASR_ERR_ARG
+ *   qasr_segment_host      the rule on the CPU: start frame, peak and silent flag of up to cap
+ *                          segments (each array may be NULL); returns the segment count (which may
+ *                          exceed cap: nothing past cap is written), or minus an error code
+ * stage level, as qasr_resample (host buffers in and out, synchronises; the pool is untouched):
+ *   qasr_segment           B recordings at 16 kHz.  e, s: [sum F] back to back (each may be NULL);
+ *                          cuts, peak, silent: [B][cap] (each may be NULL); n_seg [B]; peak_rec [B]
+ *                          (may be NULL).  A recording with more than cap segments is QASR_ERR_ARG.
+ *   qasr_segment_last_us   device time of the last qasr_segment's launches on this context in
+ *                          microseconds (HIP events around the launches alone); cut_us (may be
+ *                          NULL) receives the cut kernel's share.  Minus an error code on failure.
+ * whole path:
+ *   qasr_stage_long        B recordings (rate NULL: 16 kHz; else per recording, resampled on the
+ *                          device as qasr_stage_audio_rate) -> the pool becomes all segments in
+ *                          recording order, entry = recording offset + 160 * cut.  Returns the
+ *                          segment count, or minus an error code.  qasr_run_staged,
+ *                          qasr_run_stream_staged, qasr_score and beam, sampling and constraint
+ *                          runs then serve the pool as they do any other; qasr_run keeps its
+ *                          B <= max_batch check.  A later qasr_stage_audio* clears the table.
+ *   qasr_get_segments      the table of recording rec (0 .. B - 1 of the last qasr_stage_long): start
+ *                          (16 kHz samples from the recording's own start), n_samples, peak, silent
+ *                          of up to cap segments (each array may be NULL); returns the count of
+ *                          that recording's segments, or minus an error code (QASR_ERR_STATE
+ *                          before a qasr_stage_long and after a qasr_stage_audio*).  Segment j of
+ *                          recording r is pool entry (segments of the recordings before r) + j.
+ * Aligner models: qasr_stage_long and qasr_get_segments are QASR_ERR_STATE. */
+typedef struct {
+    int32_t max_frames, min_frames, smooth_half;
+    double skip_ratio;
+} qasr_segment_params;
+int qasr_segment_validate(const qasr_segment_params *p);
+int qasr_segment_host(const float *pcm, int n, const qasr_segment_params *p, int *cuts, double *peak, int *silent, int cap);
+int qasr_segment(qasr_ctx *c, const float *const *pcm, const int *n, int B, const qasr_segment_params *p, double *e, double *s,
+                 int *cuts, double *peak, int *silent, int *n_seg, double *peak_rec, int cap);
+int qasr_segment_last_us(qasr_ctx *c, int *cut_us);
+int qasr_stage_long(qasr_ctx *c, const float *const *pcm, const int *n, const int *rate, int B, const qasr_segment_params *p);
+int qasr_get_segments(qasr_ctx *c, int rec, long long *start, int *n_samples, double *peak, int *silent, int cap);
+
+/* test only: the segmentation kernels on B packed recordings (pcm: the recordings back to back, n [B]; a
+ * recording starts wherever the one before it ends).  The device input is followed by `guard` floats of 0xFF
+ * bytes (NaN).  Every output sits between `guard` elements of 0xFF bytes and comes back whole:
+ * e, s [guard + sum F + guard] doubles; cuts [guard + B * cap + guard] ints and peak likewise in doubles
+ * (recording b's slots at b * cap); n_seg [guard + B + guard] ints, peak_rec likewise in doubles.
+ * cap must be >= F / min_frames + 1 for every recording.  launches 2: a second pair of launches on the same
+ * device state into the *2 outputs.  tile receives the frames a workgroup of the energy kernel computes. */
+typedef struct {
+    int32_t B, guard, launches, cap;
+    qasr_segment_params prm;
+    const int32_t *n;
+    const float *pcm;
+    double *e, *s, *peak, *peak_rec;
+    int32_t *cuts, *n_seg;
+    double *e2, *s2, *peak2, *peak_rec2;
+    int32_t *cuts2, *n_seg2;
+    int32_t tile;
+} qasr_kt_segment_args;
+int qasr_kt_segment(int device, qasr_kt_segment_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,19 @@ struct score_result {
     std::string error_msg;
 };
 
+// MI355X addition (trailing): a long recording cut at its pauses (Qwen3ASR::transcribe_long)
+struct long_segment {
+    double start_s = 0.0, end_s = 0.0;   // within the recording, at 16 kHz
+    bool silent = false;                 // qasr_segment_params::skip_ratio found it silent: not decoded, empty text
+    transcribe_result result;
+};
+struct long_result {
+    std::string text;                    // the segments' texts joined by one space (empty ones left out)
+    std::vector<long_segment> segments;
+    bool success = false;
+    std::string error_msg;
+};
+
 using progress_callback_t = std::function<void(int tokens_generated, int max_tokens)>;
 
 // src/qwen3_asr.h:55-116
@@ -183,6 +196,15 @@ public:
     // 8 texts; results in input order, each text's success / error_msg its own
     std::vector<score_result> score(const float *samples, int n_samples, const std::vector<std::string> &texts,
                                     const transcribe_params &params = transcribe_params());
+
+    // a recording of any length (qasr_stage_long of qasr_capi.h; no reference counterpart): uploaded once, resampled
+    // on the device when sample_rate is not 16000, cut at its quietest points on the device (seg_params; null: cuts
+    // at most 30 s apart, nothing skipped), every segment a pool entry into the recording.  Silent segments are not
+    // decoded (empty text, success); the others go through the staged stream over max_batch() slots, or -- with
+    // beam_width >= 2, sampling, constraints or hotwords, which the stream refuses -- through qasr_run_staged in
+    // groups that fit max_batch().  The context length is that of a max_frames clip plus max_tokens
+    long_result transcribe_long(const float *samples, int n_samples, int sample_rate, const transcribe_params &params = transcribe_params(),
+                                const qasr_segment_params *seg_params = nullptr);
 
 private:
     transcribe_result transcribe_internal(const float *samples, int n_samples, const transcribe_params &params, int sample_rate = 0);

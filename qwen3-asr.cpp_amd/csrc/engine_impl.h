@@ -12,6 +12,7 @@
 //   engine_score.hip   teacher-forced scoring: the score head over prefill rows, qasr_prefill_score, qasr_score
 //   engine_align.hip   the forced aligner and its JSON output
 //   engine_resample.hip  audio at other rates: the host-only resampler entries, the tap-table cache, the resample stage
+//   engine_segment.hip  long recordings: the host-only segmentation entries, the segment stage, qasr_stage_long
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,7 @@
 #include "beam_host.h"
 #include "score_host.h"
 #include "resample_host.h"
+#include "segment_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -257,6 +259,17 @@ struct qasr_ctx {
     std::map<int, ResampleTab> rs_tabs;
     bool rs_timed = false;
     hipEvent_t rs_ev[2] = {};          // around qasr_resample's launch (qasr_resample_last_us), created by its first call
+    // pause segmentation of long recordings (engine_segment.hip): the recording and block lists of a
+    // call, e / s, the cut kernel's outputs (peak | peak_rec | cuts | n_seg in one buffer, one copy back), and the
+    // table of the last qasr_stage_long (seg_valid: the pool is that table's; any qasr_stage_audio* clears it)
+    DevBuf sgrecs, sgblocks, sg_e, sg_s, sg_out;
+    bool sg_timed = false;
+    hipEvent_t sg_ev[3] = {};          // before, between and after qasr_segment's two launches, created by its first call
+    bool seg_valid = false;
+    std::vector<int> seg_first;        // per recording: its first pool entry; one more entry: the pool size
+    std::vector<long> seg_rec_off;     // per recording: its first sample in c->pcm
+    std::vector<double> seg_peak;      // per pool entry
+    std::vector<int> seg_silent;
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -327,6 +340,7 @@ struct qasr_ctx {
         for (auto &b : owned) (void)hipFree(b.p);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : rs_ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : sg_ev) if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
         if (st) (void)hipStreamDestroy(st);
     }
@@ -453,6 +467,17 @@ struct ResampleLayout {
 int resample_table(qasr_ctx *c, int rate, ResampleTab &out);
 int resample_layout(const int *n, const int *rate, int B, ResampleLayout &o);
 int run_resample(qasr_ctx *c, const ResampleLayout &o, const float *d_in, float *d_out, bool timed = false);
+
+// engine_segment.hip
+// the segment tables of B recordings already on the device (d_pcm + off[b], n[b] samples at 16 kHz), on the context
+// stream; synchronises.  want_e: e is kept in c->sg_e beside s in c->sg_s (frame_off: each recording's first row)
+struct SegmentRun {
+    std::vector<qasr::SegmentTable> tab;
+    std::vector<long> frame_off;
+    long frames = 0;
+};
+int run_segment(qasr_ctx *c, const float *d_pcm, const std::vector<long> &off, const std::vector<int> &n,
+                const qasr::SegmentParams &p, bool want_e, bool timed, SegmentRun &out);
 
 // engine_decode.hip
 int split_bucket(qasr_ctx *c, int pos);

@@ -167,6 +167,7 @@ extern "C" int qasr_stage_audio_rate(qasr_ctx *c, const float *const *pcm, const
     int rc;
     if ((rc = resample_layout(n, rate, B, o)) || (rc = resample_host_clips(c, pcm, o, c->pcm))) return rc;
     HIPCHK(hipStreamSynchronize(c->st));
+    c->seg_valid = false;
     c->staged_n = o.n_out;   // the pool holds 16 kHz clips from here on
     c->staged_off = o.out_off;
     return 0;

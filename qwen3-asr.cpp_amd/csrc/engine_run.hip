@@ -17,6 +17,7 @@ qasr::eng::RoctxRange::~RoctxRange() { roctxRangePop(); }
 extern "C" int qasr_stage_audio(qasr_ctx *c, const float *const *pcm, const int *n, int B) {
     if (!c || !pcm || !n || B <= 0) return fail(QASR_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(c->m->device));
+    c->seg_valid = false;   // (the pool is no qasr_stage_long's from here on)
     c->staged_n.assign(n, n + B);
     c->staged_off.assign(B, 0);
     for (int b = 0; b < B; b++)

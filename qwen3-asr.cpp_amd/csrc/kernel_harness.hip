@@ -570,3 +570,64 @@ extern "C" int qasr_kt_resample(int device, qasr_kt_resample_args *a) {
     if ((rc = get(out, a->out)) || (rc = get(out2, a->out2))) return rc;
     return 0;
 }
+
+// the segmentation kernels (csrc/segment.hip) on B packed recordings.  The packed input is followed by `guard`
+// floats of 0xFF bytes; every output has `guard` elements of 0xFF bytes before and after it and comes back whole.
+// launches == 2: a second pair of launches on the same inputs and lists into the *2 outputs, laid out the same.
+extern "C" int qasr_kt_segment(int device, qasr_kt_segment_args *a) {
+    if (!a || a->B <= 0 || a->guard < 0 || a->cap < 1 || !a->n || !a->e || !a->s || !a->peak || !a->peak_rec || !a->cuts || !a->n_seg ||
+        a->launches < 1 || a->launches > 2 ||
+        (a->launches == 2 && !(a->e2 && a->s2 && a->peak2 && a->peak_rec2 && a->cuts2 && a->n_seg2)))
+        return fail(QASR_ERR_ARG, "bad arguments");
+    SegmentParams prm;
+    prm.max_frames = a->prm.max_frames; prm.min_frames = a->prm.min_frames; prm.smooth_half = a->prm.smooth_half;
+    prm.skip_ratio = a->prm.skip_ratio;
+    const std::string err = segment_validate(prm);
+    if (!err.empty()) return fail(QASR_ERR_ARG, err);
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int B = a->B, G = a->guard, cap = a->cap;
+    std::vector<SegmentRec> recs(B);
+    std::vector<int2> blocks;
+    long tot = 0, frames = 0;
+    for (int b = 0; b < B; b++) {
+        if (a->n[b] < 0) return fail(QASR_ERR_ARG, "negative length");
+        const int F = (int)segment_frames(a->n[b]);
+        if (segment_cap(a->n[b], prm) > cap) return fail(QASR_ERR_ARG, "cap below F / min_frames + 1");
+        recs[b] = SegmentRec{tot, frames, (long)b * cap, F, cap};
+        for (int f = 0; f < F; f += segment_tile()) blocks.push_back(make_int2(b, f));
+        tot += a->n[b];
+        frames += F;
+    }
+    if (tot > 0 && !a->pcm) return fail(QASR_ERR_ARG, "bad arguments");
+    KtBuf in, drecs, dblocks, e[2], s[2], peak[2], prec[2], cuts[2], nseg[2];
+    in.bytes = (size_t)(tot + G) * 4 + 256;
+    HIPCHK(hipMalloc((void **)&in.d, in.bytes));
+    HIPCHK(hipMemset(in.d, 0xFF, in.bytes));
+    if (tot) HIPCHK(hipMemcpy(in.d, a->pcm, (size_t)tot * 4, hipMemcpyHostToDevice));
+    const int2 none = make_int2(0, 0);
+    if ((rc = put_state(drecs, recs.data(), recs.size() * sizeof(SegmentRec))) ||
+        (rc = put_state(dblocks, blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(int2))))
+        return rc;
+    double *he[2] = {a->e, a->e2}, *hs[2] = {a->s, a->s2}, *hpk[2] = {a->peak, a->peak2}, *hpr[2] = {a->peak_rec, a->peak_rec2};
+    int32_t *hc[2] = {a->cuts, a->cuts2}, *hn[2] = {a->n_seg, a->n_seg2};
+    for (int l = 0; l < a->launches; l++)
+        if ((rc = put_out(e[l], he[l], frames, 1, 8, G)) || (rc = put_out(s[l], hs[l], frames, 1, 8, G)) ||
+            (rc = put_out(peak[l], hpk[l], (long)B * cap, 1, 8, G)) || (rc = put_out(prec[l], hpr[l], B, 1, 8, G)) ||
+            (rc = put_out(cuts[l], hc[l], (long)B * cap, 1, 4, G)) || (rc = put_out(nseg[l], hn[l], B, 1, 4, G)))
+            return rc;
+    for (int l = 0; l < a->launches; l++)
+        launch_segment(in.ptr<float>(), drecs.ptr<SegmentRec>(), B, dblocks.ptr<int2>(), (int)blocks.size(), prm.max_frames,
+                       prm.min_frames, prm.smooth_half, e[l].ptr<double>(), s[l].ptr<double>(), cuts[l].ptr<int>(), peak[l].ptr<double>(),
+                       nseg[l].ptr<int>(), prec[l].ptr<double>(), nullptr);
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipDeviceSynchronize();
+    if (le != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (se != hipSuccess) return fail(QASR_ERR_DEVICE, std::string("kernel run: ") + hipGetErrorString(se));
+    a->tile = segment_tile();
+    for (int l = 0; l < a->launches; l++)
+        if ((rc = get(e[l], he[l])) || (rc = get(s[l], hs[l])) || (rc = get(peak[l], hpk[l])) || (rc = get(prec[l], hpr[l])) ||
+            (rc = get(cuts[l], hc[l])) || (rc = get(nseg[l], hn[l])))
+            return rc;
+    return 0;
+}

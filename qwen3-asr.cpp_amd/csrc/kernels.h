@@ -40,6 +40,23 @@ int resample_tile();
 // a plan the kernel's LDS window holds (every supported rate does; the engine checks it before a launch)
 bool resample_fits(int L, int M, int H);
 
+// ---------------------------------------------------------------- pause segmentation of long recordings
+// One entry per recording (csrc/segment_host.h states the rule): its samples in the PCM buffer, its frames
+// F = n / 160, where its e / s rows start (in frames) and where its cut-kernel outputs start (in segments; cap of
+// them at most, cap >= F / min_frames + 1).
+struct SegmentRec {
+    long off;        // first sample of the recording in the PCM buffer
+    long frame_off;  // first frame of the recording in e / s
+    long seg_off;    // first segment slot of the recording in cuts / peak
+    int F, cap;
+};
+// seg_energy_kernel: blocks = (recording, first frame of the tile), segment_tile() frames a block; e may be null.
+// seg_cut_kernel: one block a recording; cuts / peak [sum cap], n_seg / peak_rec [B].
+void launch_segment(const float *pcm, const SegmentRec *recs, int B, const int2 *blocks, int n_blocks, int max_frames,
+                    int min_frames, int H, double *e, double *s, int *cuts, double *peak, int *n_seg, double *peak_rec,
+                    hipStream_t st, hipEvent_t between = nullptr);
+int segment_tile();
+
 // ---------------------------------------------------------------- conv front-end
 // One entry per 100-frame mel chunk (src/audio_encoder.cpp:331-409).
 // conv2 / conv3 weight row length: 9 * channels rounded up to 128, zeros past 9 * channels

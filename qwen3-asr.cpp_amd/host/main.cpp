@@ -51,6 +51,10 @@ struct cli_params {
     std::vector<std::string> hotwords;
     std::vector<float> hotword_boosts;
     float hotword_boost = 5.f;
+    // --long / --segment-max / --segment-min / --skip-silence / --segments: one -f recording of any length, cut at its
+    // pauses on the device (Qwen3ASR::transcribe_long)
+    bool long_mode = false, print_segments = false;
+    double segment_max_s = 30.0, segment_min_s = 10.0, skip_silence_db = 1.0;   // (skip_silence_db > 0: nothing skipped)
     std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
 };
@@ -85,6 +89,12 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --hotword <text>       Prefer this word or phrase (repeatable; at most 16 tokens each)\n");
     fprintf(stderr, "  --hotwords-file <path> One hotword a line, optionally a tab and its own boost; lines starting with # are comments\n");
     fprintf(stderr, "  --hotword-boost <b>    Added to the next token's logit while a hotword is being spelled, 0 < b <= 100 (default 5)\n");
+    fprintf(stderr, "  --long                 Take the one -f file at any length: cut at its quietest points on the GPU into segments\n");
+    fprintf(stderr, "                         that are decoded from the uploaded recording (any --resample rate is accepted)\n");
+    fprintf(stderr, "  --segment-max <s>      With --long: the longest segment in seconds (default 30)\n");
+    fprintf(stderr, "  --segment-min <s>      With --long: the shortest segment in seconds, at most half of --segment-max (default 10)\n");
+    fprintf(stderr, "  --skip-silence <dB>    With --long: do not decode segments whose peak energy is <dB> (<= 0) or more below the recording's\n");
+    fprintf(stderr, "  --segments             With --long: one '[start --> end] text' line a segment instead of the joined text\n");
     fprintf(stderr, "  --score <text>         Score <text> as a transcript of the -f file instead of transcribing (repeatable):\n");
     fprintf(stderr, "                         per text the summed log-probability, the mean per token and the token count\n");
     fprintf(stderr, "                         (the EOS included); with --tokens every token's id, text and log-probability,\n");
@@ -145,6 +155,15 @@ static bool parse(int argc, char **argv, cli_params &p) {
         else if (!strcmp(a, "--progress")) p.print_progress = true;
         else if (!strcmp(a, "--no-timing")) p.print_timing = false;
         else if (!strcmp(a, "--resample")) p.resample = true;
+        else if (!strcmp(a, "--long")) p.long_mode = true;
+        else if (!strcmp(a, "--segments")) p.print_segments = true;
+        else if (!strcmp(a, "--segment-max")) { if (!val(v)) return false; p.segment_max_s = atof(v.c_str()); }
+        else if (!strcmp(a, "--segment-min")) { if (!val(v)) return false; p.segment_min_s = atof(v.c_str()); }
+        else if (!strcmp(a, "--skip-silence")) {
+            if (!val(v)) return false;
+            p.skip_silence_db = atof(v.c_str());
+            if (!(p.skip_silence_db <= 0.0)) { fprintf(stderr, "Error: --skip-silence takes a level in dB <= 0\n"); return false; }
+        }
         else if (!strcmp(a, "--tokens")) p.print_tokens = true;
         else if (!strcmp(a, "--logprobs")) p.logprobs = true;
         else if (!strcmp(a, "--top-k")) {
@@ -262,6 +281,10 @@ static bool parse(int argc, char **argv, cli_params &p) {
     if (p.audio_paths.empty()) { fprintf(stderr, "Error: Audio file path is required (-f/--audio)\n"); return false; }
     if (!p.score_texts.empty() && (p.audio_paths.size() != 1 || p.align_mode || p.transcribe_align_mode || !p.devices.empty())) {
         fprintf(stderr, "Error: --score takes one -f file and no alignment or --devices\n");
+        return false;
+    }
+    if (p.long_mode && (p.audio_paths.size() != 1 || p.align_mode || p.transcribe_align_mode || !p.devices.empty() || !p.score_texts.empty())) {
+        fprintf(stderr, "Error: --long takes one -f file and no alignment, --score or --devices\n");
         return false;
     }
     // src/main.cpp:76-90
@@ -557,6 +580,34 @@ static int run_transcription_sharded(const cli_params &p) {
     return write_output(p, all);
 }
 
+// --long: the one recording through Qwen3ASR::transcribe_long
+static int run_long(const cli_params &p, qwen3_asr::Qwen3ASR &asr, const qwen3_asr::transcribe_params &tp) {
+    std::vector<float> pcm;
+    int sr = 0;
+    if (!qwen3_asr::load_audio_file(p.audio_paths[0], pcm, sr)) { fprintf(stderr, "Error: Failed to load audio file: %s\n", p.audio_paths[0].c_str()); return 1; }
+    if (sr != 16000 && !p.resample) { fprintf(stderr, "Error: Audio must be 16kHz, got %d Hz\n", sr); return 1; }
+    // seconds -> frames of 10 ms; dB -> the energy ratio 10^(dB / 10) the engine compares with
+    qasr_segment_params sp{(int32_t)std::llround(p.segment_max_s * 100.0), (int32_t)std::llround(p.segment_min_s * 100.0), 5,
+                           p.skip_silence_db <= 0.0 ? std::pow(10.0, p.skip_silence_db / 10.0) : -1.0};
+    asr.set_max_batch(p.batch);
+    const qwen3_asr::long_result r = asr.transcribe_long(pcm.data(), (int)pcm.size(), sr, tp, &sp);
+    if (!r.success) { fprintf(stderr, "Error: %s\n", r.error_msg.c_str()); return 1; }
+    std::string all;
+    size_t n_silent = 0;
+    for (const auto &s : r.segments) {
+        n_silent += s.silent;
+        if (!p.print_segments) continue;
+        char head[64];
+        snprintf(head, sizeof head, "[%.2f --> %.2f] ", s.start_s, s.end_s);
+        all += head + s.result.text + "\n";
+    }
+    if (!p.print_segments) all = r.text + "\n";
+    fprintf(stderr, "%s: %.1f s in %zu segments (%zu silent, not decoded)\n", p.audio_paths[0].c_str(), pcm.size() / (double)sr, r.segments.size(), n_silent);
+    const int rc = write_output(p, all);
+    if (p.profile) fprintf(stderr, "%s", asr.profile_report().c_str());
+    return rc;
+}
+
 static int run_transcription(const cli_params &p) {
     fprintf(stderr, "qwen3-asr-cli\n  Model: %s\n", p.model_path.c_str());
     for (auto &a : p.audio_paths) fprintf(stderr, "  Audio: %s\n", a.c_str());
@@ -587,6 +638,7 @@ static int run_transcription(const cli_params &p) {
     tp.hotword_boost = p.hotword_boost;
     tp.hotword_boosts = p.hotword_boosts;
     tp.resample = p.resample;
+    if (p.long_mode) return run_long(p, asr, tp);
     std::vector<qwen3_asr::transcribe_result> results;
     if (p.audio_paths.size() == 1) {
         results.push_back(asr.transcribe(p.audio_paths[0], tp));

@@ -225,6 +225,97 @@ transcribe_result Qwen3ASR::transcribe(const float *samples, int n_samples, cons
     return transcribe_internal(samples, n_samples, params);
 }
 
+// the results of the last qasr_run / qasr_run_staged of out.size() clips (toks [B][max_tokens], nt [B]) as the call
+// asked for them: per-token values, alternatives, beam and sampling hypotheses, texts.  A message: every clip failed
+static std::string collect_run(qasr_ctx *ctx, qasr_model *model, const transcribe_params &params, const std::vector<int32_t> &toks,
+                               const std::vector<int> &nt, const qasr_timings &tm, int64_t t0, std::vector<transcribe_result> &out) {
+    const int B = (int)out.size();
+    const int W = params.beam_width >= 2 ? params.beam_width : 1;
+    const bool beam = W >= 2, sampling = params.temperature > 0.f;
+    const int NB = sampling ? std::max(params.n_best, 1) : 1;
+    const bool many = sampling && NB >= 2;
+    const bool want_lp = params.token_logprobs && !beam && !many;
+    std::vector<float> lps;
+    if (want_lp) {
+        lps.resize((size_t)B * params.max_tokens);
+        if (qasr_get_logprobs(ctx, lps.data(), B, params.max_tokens) != 0) {
+            return std::string("Decoding failed: ") + qasr_last_error();
+        }
+    }
+    const int K = beam || many ? 0 : params.top_k;
+    std::vector<int32_t> alt_id;
+    std::vector<float> alt_lp;
+    if (K > 0) {
+        alt_id.resize((size_t)B * params.max_tokens * K);
+        alt_lp.resize(alt_id.size());
+        if (qasr_get_topk(ctx, alt_id.data(), alt_lp.data(), B, params.max_tokens, K) != 0) {
+            return std::string("Decoding failed: ") + qasr_last_error();
+        }
+    }
+    const int64_t t1 = now_ms();
+    for (int b = 0; b < B; b++) {
+        transcribe_result &r = out[b];
+        r.tokens.assign(toks.begin() + (long)b * params.max_tokens, toks.begin() + (long)b * params.max_tokens + nt[b]);
+        if (want_lp)
+            r.token_logprobs.assign(lps.begin() + (long)b * params.max_tokens, lps.begin() + (long)b * params.max_tokens + nt[b]);
+        if (K > 0) {
+            const long o = (long)b * params.max_tokens * K;
+            r.alt_tokens.assign(alt_id.begin() + o, alt_id.begin() + o + (long)nt[b] * K);
+            r.alt_logprobs.assign(alt_lp.begin() + o, alt_lp.begin() + o + (long)nt[b] * K);
+        }
+        auto detok = [&](const std::vector<int32_t> &t) {
+            const int len = qasr_detokenize(model, t.data(), (int)t.size(), nullptr, 0);
+            std::string text(std::max(len, 0) + 1, '\0');
+            qasr_detokenize(model, t.data(), (int)t.size(), &text[0], (int)text.size());
+            text.resize(std::max(len, 0));
+            return text;
+        };
+        r.text = detok(r.tokens);
+        if (beam) {
+            std::vector<int32_t> bt((size_t)W * params.max_tokens);
+            std::vector<int> bn(W), bf(W);
+            std::vector<float> bs(W);
+            const int nh = qasr_get_beams(ctx, b, bt.data(), nullptr, bn.data(), bs.data(), bf.data(), W, params.max_tokens);
+            if (nh < 0) {
+                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+                continue;
+            }
+            for (int i = 0; i < nh; i++) {
+                beam_hypothesis h;
+                h.tokens.assign(bt.begin() + (long)i * params.max_tokens, bt.begin() + (long)i * params.max_tokens + bn[i]);
+                h.text = detok(h.tokens);
+                h.sum_logprob = bs[i];
+                h.finished = bf[i] != 0;
+                r.beams.push_back(std::move(h));
+            }
+        }
+        if (sampling) {
+            std::vector<int32_t> st((size_t)NB * params.max_tokens);
+            std::vector<float> sl(st.size()), ss(NB);
+            std::vector<int> sn(NB);
+            const int nh = qasr_get_samples(ctx, b, st.data(), sl.data(), sn.data(), ss.data(), NB, params.max_tokens);
+            if (nh < 0) {
+                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
+                continue;
+            }
+            for (int i = 0; i < nh; i++) {
+                sample_hypothesis h;
+                h.tokens.assign(st.begin() + (long)i * params.max_tokens, st.begin() + (long)i * params.max_tokens + sn[i]);
+                h.token_logprobs.assign(sl.begin() + (long)i * params.max_tokens, sl.begin() + (long)i * params.max_tokens + sn[i]);
+                h.text = detok(h.tokens);
+                h.sum_logprob = ss[i];
+                r.samples.push_back(std::move(h));
+            }
+        }
+        r.success = true;
+        r.t_mel_ms = (int64_t)tm.t_mel_ms;
+        r.t_encode_ms = (int64_t)tm.t_encode_ms;
+        r.t_decode_ms = (int64_t)(tm.t_prefill_ms + tm.t_decode_ms);
+        r.t_total_ms = t1 - t0;
+    }
+    return std::string();
+}
+
 // one clip through qasr_run: the stage timings and --profile sections of the
 // reference's transcribe_internal (src/qwen3_asr.cpp:81-160)
 // rates: the clips' sample rates (null: 16 kHz), resampled on the device before the mel stage
@@ -287,87 +378,9 @@ std::vector<transcribe_result> Qwen3ASR::transcribe_run(const std::vector<std::v
         rep.resize(std::max(len, 0));
         profile_report_ = rep;
     }
-    const bool want_lp = params.token_logprobs && !beam && !many;
-    std::vector<float> lps;
-    if (want_lp) {
-        lps.resize((size_t)B * params.max_tokens);
-        if (qasr_get_logprobs(ctx_, lps.data(), B, params.max_tokens) != 0) {
-            for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
-            return out;
-        }
-    }
-    const int K = beam || many ? 0 : params.top_k;
-    std::vector<int32_t> alt_id;
-    std::vector<float> alt_lp;
-    if (K > 0) {
-        alt_id.resize((size_t)B * params.max_tokens * K);
-        alt_lp.resize(alt_id.size());
-        if (qasr_get_topk(ctx_, alt_id.data(), alt_lp.data(), B, params.max_tokens, K) != 0) {
-            for (auto &r : out) r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
-            return out;
-        }
-    }
-    const int64_t t1 = now_ms();
-    for (int b = 0; b < B; b++) {
-        transcribe_result &r = out[b];
-        r.tokens.assign(toks.begin() + (long)b * params.max_tokens, toks.begin() + (long)b * params.max_tokens + nt[b]);
-        if (want_lp)
-            r.token_logprobs.assign(lps.begin() + (long)b * params.max_tokens, lps.begin() + (long)b * params.max_tokens + nt[b]);
-        if (K > 0) {
-            const long o = (long)b * params.max_tokens * K;
-            r.alt_tokens.assign(alt_id.begin() + o, alt_id.begin() + o + (long)nt[b] * K);
-            r.alt_logprobs.assign(alt_lp.begin() + o, alt_lp.begin() + o + (long)nt[b] * K);
-        }
-        auto detok = [&](const std::vector<int32_t> &t) {
-            const int len = qasr_detokenize(model_, t.data(), (int)t.size(), nullptr, 0);
-            std::string text(std::max(len, 0) + 1, '\0');
-            qasr_detokenize(model_, t.data(), (int)t.size(), &text[0], (int)text.size());
-            text.resize(std::max(len, 0));
-            return text;
-        };
-        r.text = detok(r.tokens);
-        if (beam) {
-            std::vector<int32_t> bt((size_t)W * params.max_tokens);
-            std::vector<int> bn(W), bf(W);
-            std::vector<float> bs(W);
-            const int nh = qasr_get_beams(ctx_, b, bt.data(), nullptr, bn.data(), bs.data(), bf.data(), W, params.max_tokens);
-            if (nh < 0) {
-                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
-                continue;
-            }
-            for (int i = 0; i < nh; i++) {
-                beam_hypothesis h;
-                h.tokens.assign(bt.begin() + (long)i * params.max_tokens, bt.begin() + (long)i * params.max_tokens + bn[i]);
-                h.text = detok(h.tokens);
-                h.sum_logprob = bs[i];
-                h.finished = bf[i] != 0;
-                r.beams.push_back(std::move(h));
-            }
-        }
-        if (sampling) {
-            std::vector<int32_t> st((size_t)NB * params.max_tokens);
-            std::vector<float> sl(st.size()), ss(NB);
-            std::vector<int> sn(NB);
-            const int nh = qasr_get_samples(ctx_, b, st.data(), sl.data(), sn.data(), ss.data(), NB, params.max_tokens);
-            if (nh < 0) {
-                r.error_msg = std::string("Decoding failed: ") + qasr_last_error();
-                continue;
-            }
-            for (int i = 0; i < nh; i++) {
-                sample_hypothesis h;
-                h.tokens.assign(st.begin() + (long)i * params.max_tokens, st.begin() + (long)i * params.max_tokens + sn[i]);
-                h.token_logprobs.assign(sl.begin() + (long)i * params.max_tokens, sl.begin() + (long)i * params.max_tokens + sn[i]);
-                h.text = detok(h.tokens);
-                h.sum_logprob = ss[i];
-                r.samples.push_back(std::move(h));
-            }
-        }
-        r.success = true;
-        r.t_mel_ms = (int64_t)tm.t_mel_ms;
-        r.t_encode_ms = (int64_t)tm.t_encode_ms;
-        r.t_decode_ms = (int64_t)(tm.t_prefill_ms + tm.t_decode_ms);
-        r.t_total_ms = t1 - t0;
-    }
+    const std::string err = collect_run(ctx_, model_, params, toks, nt, tm, t0, out);
+    if (!err.empty())
+        for (auto &r : out) r.error_msg = err;
     return out;
 }
 
@@ -436,7 +449,14 @@ struct StreamCtx {
     qasr_ctx *lp_ctx;   // non-null: transcribe_params::token_logprobs
     qasr_ctx *tk_ctx;   // non-null: transcribe_params::top_k, its value in top_k
     int top_k;
+    const std::vector<int> *staged = nullptr;   // transcribe_long: the pool entries to decode, in order
+    size_t staged_next = 0;
 };
+// (the staged stream: the clip is pool entry id, already in HBM)
+int stream_fetch_staged(void *u, int *) {
+    StreamCtx *s = (StreamCtx *)u;
+    return s->staged_next < s->staged->size() ? (*s->staged)[s->staged_next++] : -1;
+}
 int stream_fetch_rate(void *u, const float **pcm, int *n, int *rate, int *) {
     StreamCtx *s = (StreamCtx *)u;
     int id = -1, sr = 16000;
@@ -530,6 +550,101 @@ bool Qwen3ASR::stream_impl(const std::function<bool(int &id, std::vector<float> 
         profile_report_ = rep;
     }
     return true;
+}
+
+// a recording of any length: staged once (qasr_stage_long: resampled and cut on the device, every segment a pool entry
+// into the recording), then the segments that are not silent decoded from the pool
+long_result Qwen3ASR::transcribe_long(const float *samples, int n_samples, int sample_rate, const transcribe_params &params,
+                                      const qasr_segment_params *seg_params) {
+    long_result out;
+    if (!model_) { out.error_msg = "Model not loaded"; return out; }
+    const qasr_segment_params seg = seg_params ? *seg_params : qasr_segment_params{3000, 1000, 5, -1.0};
+    if (qasr_segment_validate(&seg) != 0) { out.error_msg = std::string("Segmentation failed: ") + qasr_last_error(); return out; }
+    std::vector<int32_t> sys;
+    if (!params.system_prompt.empty()) {
+        const int k = qasr_tokenize(model_, params.system_prompt.c_str(), nullptr, 0);
+        sys.resize(std::max(k, 0));
+        qasr_tokenize(model_, params.system_prompt.c_str(), sys.data(), k);
+    }
+    const int W = params.beam_width >= 2 ? params.beam_width : 1;
+    const int NB = params.temperature > 0.f ? std::max(params.n_best, 1) : 1;
+    const bool grouped = W >= 2 || params.temperature > 0.f || constraints_asked(params);   // (what the stream refuses)
+    // the longest segment: max_frames frames and the recording's tail of less than a frame
+    const int need = qasr_prompt_len(qasr_encoder_frames(qasr_mel_frames(seg.max_frames * 160 + 159))) + (int)sys.size() + params.max_tokens;
+    const int rows = grouped ? std::max(W, NB) * std::max(1, max_batch_ / std::max(W, NB)) : max_batch_;
+    if (!ensure_ctx(rows, need) || !set_logprobs(params.token_logprobs) || !set_top_k(params.top_k) ||
+        !set_beam_width(grouped ? params.beam_width : 0) || !set_sampling(params) || !set_constraints(params) || !set_hotwords(params)) {
+        out.error_msg = error_msg_;
+        return out;
+    }
+    qasr_set_system_prompt(ctx_, sys.data(), (int)sys.size());
+    qasr_set_profile(ctx_, profile_ ? 1 : 0);
+    const int64_t t0 = now_ms();
+    const int rate = sample_rate > 0 ? sample_rate : 16000;
+    const int K = qasr_stage_long(ctx_, &samples, &n_samples, rate == 16000 ? nullptr : &rate, 1, &seg);
+    if (K < 0) { out.error_msg = std::string("Segmentation failed: ") + qasr_last_error(); return out; }
+    std::vector<long long> start(K);
+    std::vector<int> len(K), silent(K);
+    if (qasr_get_segments(ctx_, 0, start.data(), len.data(), nullptr, silent.data(), K) != K) {
+        out.error_msg = std::string("Segmentation failed: ") + qasr_last_error();
+        return out;
+    }
+    out.segments.resize(K);
+    std::vector<int> todo;
+    for (int k = 0; k < K; k++) {
+        long_segment &s = out.segments[k];
+        s.start_s = (double)start[k] / 16000.0;
+        s.end_s = (double)(start[k] + len[k]) / 16000.0;
+        s.silent = silent[k] != 0;
+        if (s.silent) s.result.success = true;
+        else todo.push_back(k);
+    }
+    if (grouped) {
+        const size_t per = (size_t)std::max(1, max_batch_ / std::max(W, NB));
+        for (size_t i = 0; i < todo.size(); i += per) {
+            const int B = (int)std::min(per, todo.size() - i);
+            std::vector<int32_t> toks((size_t)B * params.max_tokens);
+            std::vector<int> nt(B);
+            qasr_timings tm{};
+            std::vector<transcribe_result> res(B);
+            std::string err;
+            if (qasr_run_staged(ctx_, todo.data() + i, B, params.max_tokens, 0, toks.data(), nt.data(), &tm) != 0)
+                err = std::string("Decoding failed: ") + qasr_last_error();
+            else
+                err = collect_run(ctx_, model_, params, toks, nt, tm, t0, res);
+            for (int b = 0; b < B; b++) {
+                if (!err.empty()) res[b].error_msg = err;
+                out.segments[todo[i + b]].result = std::move(res[b]);
+            }
+        }
+    } else if (!todo.empty()) {
+        const std::function<void(int, transcribe_result)> sink = [&](int id, transcribe_result r) { out.segments[id].result = std::move(r); };
+        TokenCb tcb{&progress_callback_, params.max_tokens, params.print_progress};
+        const bool per_token = progress_callback_ || params.print_progress;
+        qasr_set_token_callback(ctx_, per_token ? stream_token_cb : nullptr, per_token ? &tcb : nullptr);
+        StreamCtx sc{nullptr, &sink, model_, {}, t0, params.token_logprobs ? ctx_ : nullptr, params.top_k > 0 ? ctx_ : nullptr, params.top_k, &todo, 0};
+        const int rc = qasr_run_stream_staged(ctx_, std::min((int)todo.size(), max_batch_), stream_fetch_staged, stream_sink, &sc, params.max_tokens, 0, nullptr);
+        qasr_set_token_callback(ctx_, nullptr, nullptr);
+        if (rc != 0) { out.error_msg = std::string("Decoding failed: ") + qasr_last_error(); return out; }
+    }
+    if (profile_) {
+        const int plen = qasr_profile_report(ctx_, nullptr, 0);
+        std::string rep(std::max(plen, 0) + 1, '\0');
+        qasr_profile_report(ctx_, &rep[0], (int)rep.size());
+        rep.resize(std::max(plen, 0));
+        profile_report_ = rep;
+    }
+    out.success = true;
+    for (const long_segment &s : out.segments) {
+        if (!s.result.success) {
+            out.success = false;
+            if (out.error_msg.empty()) out.error_msg = s.result.error_msg.empty() ? "A segment was not decoded" : s.result.error_msg;
+        }
+        if (s.result.text.empty()) continue;
+        if (!out.text.empty()) out.text += ' ';
+        out.text += s.result.text;
+    }
+    return out;
 }
 
 // sample_rate 0: 16 kHz PCM; else the resampler in front (qasr_transcribe_batch_rate)

@@ -43,6 +43,7 @@ EXPORTS = [
     "qasr_phrases_validate", "qasr_set_phrases", "qasr_get_phrases", "qasr_phrase_tokenize",
     "qasr_resample_plan", "qasr_resample_len", "qasr_resample_taps", "qasr_resample_host",
     "qasr_resample", "qasr_resample_last_us", "qasr_stage_audio_rate", "qasr_transcribe_batch_rate", "qasr_run_stream_rate",
+    "qasr_segment_validate", "qasr_segment_host", "qasr_segment", "qasr_segment_last_us", "qasr_stage_long", "qasr_get_segments",
 ]
 
 
@@ -84,6 +85,11 @@ class Phrases(C.Structure):
                 ("boost", C.POINTER(C.c_float))]
 
 
+class SegmentParams(C.Structure):
+    """qasr_segment_params"""
+    _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("smooth_half", C.c_int32), ("skip_ratio", C.c_double)]
+
+
 QASR_BEAM_MAX = 8
 QASR_SAMPLE_MAX = 8
 QASR_NGRAM_MAX = 8
@@ -117,7 +123,7 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libqasr.so not built at {LIB_PATH} (run __graft_entry__.build())")
         L = C.CDLL(LIB_PATH)
         P, I, F = C.c_void_p, C.c_int, C.POINTER(C.c_float)
-        I32P, IP = C.POINTER(C.c_int32), C.POINTER(C.c_int)
+        I32P, IP, DP = C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_double)
         sig = {
             "qasr_last_error": ([], C.c_char_p), "qasr_version": ([], C.c_char_p),
             "qasr_device_count": ([IP], I),
@@ -172,6 +178,12 @@ def lib() -> C.CDLL:
             "qasr_stage_audio_rate": ([P, C.POINTER(F), IP, IP, I], I),
             "qasr_transcribe_batch_rate": ([P, C.POINTER(F), IP, IP, I, I, I, I32P, IP, C.POINTER(Timings)], I),
             "qasr_run_stream_rate": ([P, I, FETCH_RATE_FN, SINK_FN, P, I, I, C.POINTER(StreamStats)], I),
+            "qasr_segment_validate": ([C.POINTER(SegmentParams)], I),
+            "qasr_segment_host": ([F, I, C.POINTER(SegmentParams), IP, DP, IP, I], I),
+            "qasr_segment": ([P, C.POINTER(F), IP, I, C.POINTER(SegmentParams), DP, DP, IP, DP, IP, IP, DP, I], I),
+            "qasr_segment_last_us": ([P, IP], I),
+            "qasr_stage_long": ([P, C.POINTER(F), IP, IP, I, C.POINTER(SegmentParams)], I),
+            "qasr_get_segments": ([P, I, C.POINTER(C.c_longlong), IP, DP, IP, I], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -337,6 +349,41 @@ def resample_host(pcm: np.ndarray, rate: int) -> np.ndarray:
     out = np.zeros(max(resample_len(len(pcm), rate), 1), np.float32)
     n = _neg(lib().qasr_resample_host(_f(pcm), len(pcm), int(rate), _f(out)), "qasr_resample_host")
     return out[:n]
+
+
+# ---- pause segmentation of long recordings (host only) ----
+def _d(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def segment_params(max_frames: int = 3000, min_frames: int = 1000, smooth_half: int = 5, skip_ratio: float = -1.0) -> SegmentParams:
+    return SegmentParams(int(max_frames), int(min_frames), int(smooth_half), float(skip_ratio))
+
+
+def segment_validate(**kw) -> None:
+    """raises QasrError naming the violated range (qasr_segment_validate)"""
+    p = segment_params(**kw)
+    _check(lib().qasr_segment_validate(C.byref(p)), "qasr_segment_validate")
+
+
+@dataclass
+class Segment:
+    rec: int          # the recording it belongs to
+    start: int        # 16 kHz samples from the recording's own start
+    n: int            # samples
+    peak: float       # the maximum smoothed energy of its frames
+    silent: bool
+
+
+def segment_host(pcm: np.ndarray, **kw) -> List["Segment"]:
+    """the rule on the CPU (qasr_segment_host): the reference of the device segmentation"""
+    pcm = np.ascontiguousarray(pcm, np.float32)
+    p = segment_params(**kw)
+    K = _neg(lib().qasr_segment_host(_f(pcm), len(pcm), C.byref(p), None, None, None, 0), "qasr_segment_host")
+    cuts, peak, silent = np.zeros(K, np.int32), np.zeros(K, np.float64), np.zeros(K, np.int32)
+    _neg(lib().qasr_segment_host(_f(pcm), len(pcm), C.byref(p), _i(cuts), _d(peak), _i(silent), K), "qasr_segment_host")
+    ends = [int(c) * 160 for c in cuts[1:]] + [len(pcm)]
+    return [Segment(0, int(cuts[k]) * 160, ends[k] - int(cuts[k]) * 160, float(peak[k]), bool(silent[k])) for k in range(K)]
 
 
 def fix_timestamps(classes: Sequence[int]) -> List[int]:
@@ -580,6 +627,38 @@ class Context:
             res.append(out[o:o + k].copy())
             o += k
         return res
+
+    def segment(self, recs: Sequence[np.ndarray], want_energy: bool = False, **kw):
+        """qasr_segment: recordings at 16 kHz -> per recording its List[Segment], cut on the device (the pool stays as it
+        is).  want_energy: -> (segments, e per recording, s per recording), the frame and smoothed energies (float64)"""
+        recs = [np.ascontiguousarray(c, np.float32) for c in recs]
+        B = len(recs)
+        n = np.array([len(c) for c in recs], np.int32)
+        p = segment_params(**kw)
+        _check(lib().qasr_segment_validate(C.byref(p)), "qasr_segment_validate")
+        F = [int(k) // 160 for k in n]
+        cap = max(f // p.min_frames + 1 for f in F)
+        e, s = np.zeros(max(1, sum(F)), np.float64), np.zeros(max(1, sum(F)), np.float64)
+        cuts, peak, silent = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.float64), np.zeros((B, cap), np.int32)
+        nseg = np.zeros(B, np.int32)
+        ptrs = (C.POINTER(C.c_float) * B)(*[_f(c) for c in recs])
+        _check(lib().qasr_segment(self.h, ptrs, _i(n), B, C.byref(p), _d(e) if want_energy else None, _d(s) if want_energy else None,
+                                  _i(cuts), _d(peak), _i(silent), _i(nseg), None, cap), "qasr_segment")
+        out = []
+        for b in range(B):
+            K = int(nseg[b])
+            ends = [int(c) * 160 for c in cuts[b, 1:K]] + [int(n[b])]
+            out.append([Segment(b, int(cuts[b, k]) * 160, ends[k] - int(cuts[b, k]) * 160, float(peak[b, k]), bool(silent[b, k]))
+                        for k in range(K)])
+        if not want_energy:
+            return out
+        o = np.concatenate([[0], np.cumsum(F)])
+        return out, [e[o[b]:o[b + 1]].copy() for b in range(B)], [s[o[b]:o[b + 1]].copy() for b in range(B)]
+
+    def segment_last_us(self) -> Tuple[int, int]:
+        """device time of the last segment() call's launches and the cut kernel's share of it, microseconds"""
+        cut = C.c_int(0)
+        return _neg(lib().qasr_segment_last_us(self.h, C.byref(cut)), "qasr_segment_last_us"), cut.value
 
     def resample_last_us(self) -> int:
         """device time of the last resample() call's kernel launch, microseconds"""
@@ -1057,3 +1136,59 @@ class Context:
     def transcribe(self, clips, max_tokens=1024, ignore_eos=False, rates=None) -> RunResult:
         self.stage_audio(clips, rates)
         return self.run(max_tokens, ignore_eos)
+
+    # ---- long recordings ------------------------------------
+    def stage_long(self, recs: Sequence[np.ndarray], rates: Optional[Sequence[int]] = None, **kw) -> List[Segment]:
+        """qasr_stage_long: the recordings are uploaded once (resampled on the device where rates says so) and cut at
+        their pauses on the device; the pool becomes the segments, in recording order, each pointing into its
+        recording.  Returns the table (entry k is pool clip k for run_staged / run_stream_staged / score)"""
+        recs = [np.ascontiguousarray(c, np.float32) for c in recs]
+        n = np.array([len(c) for c in recs], np.int32)
+        ptrs = (C.POINTER(C.c_float) * len(recs))(*[_f(c) for c in recs])
+        r = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, np.int32)
+            if len(r) != len(recs):
+                raise QasrError("stage_long: one rate per recording")
+        p = segment_params(**kw)
+        K = _neg(lib().qasr_stage_long(self.h, ptrs, _i(n), _i(r) if r is not None else None, len(recs), C.byref(p)), "qasr_stage_long")
+        self._staged = [None] * K   # (the pool size run() checks)
+        self._long_recs = len(recs)
+        return self.get_segments()
+
+    def get_segments(self, rec: Optional[int] = None) -> List[Segment]:
+        """qasr_get_segments: the table of the last stage_long, of one recording or of all in pool order"""
+        if rec is None:
+            return [s for b in range(getattr(self, "_long_recs", 1)) for s in self.get_segments(b)]
+        K = _neg(lib().qasr_get_segments(self.h, int(rec), None, None, None, None, 0), "qasr_get_segments")
+        start, n = np.zeros(K, np.int64), np.zeros(K, np.int32)
+        peak, silent = np.zeros(K, np.float64), np.zeros(K, np.int32)
+        _neg(lib().qasr_get_segments(self.h, int(rec), start.ctypes.data_as(C.POINTER(C.c_longlong)), _i(n), _d(peak), _i(silent), K),
+             "qasr_get_segments")
+        return [Segment(int(rec), int(start[k]), int(n[k]), float(peak[k]), bool(silent[k])) for k in range(K)]
+
+    def transcribe_long(self, pcm: np.ndarray, max_tokens: int = 1024, ignore_eos: bool = False, rate: int = 16000, **kw):
+        """one recording of any length: stage_long, then every segment that is not silent through the staged stream
+        (beam search, sampling, constraints or hotwords on, which the stream refuses: run_staged in groups of
+        max_batch).  -> (text, [(Segment, tokens)]): silent segments have no tokens, text joins the others' by a space"""
+        segs = self.stage_long([pcm], None if rate == 16000 else [rate], **kw)
+        todo = [k for k, s in enumerate(segs) if not s.silent]
+        toks = {k: [] for k in range(len(segs))}
+        cons = self.get_constraints()
+        grouped = self._beam_on() or self._sampling_on() or bool(self.get_phrases()) or bool(
+            cons["no_repeat_ngram"] or cons["repetition_penalty"] != 1.0 or len(cons["bias"]))
+        if grouped:
+            per = max(1, self.max_batch // max(self.get_option("beam_width"), self.get_sampling().n_best, 1))
+            for i in range(0, len(todo), per):
+                r = self.run_staged(todo[i:i + per], max_tokens, ignore_eos)
+                for k, t in zip(todo[i:i + per], r.tokens):
+                    toks[k] = list(t)
+        elif todo:
+            it = iter(todo)
+            res, _ = self.run_stream_staged(lambda: next(it, None), max_tokens, ignore_eos)
+            for k in todo:
+                if isinstance(res.get(k), Exception):
+                    raise res[k]
+                toks[k] = list(res[k])
+        texts = [self.model.detokenize(toks[k]) for k in todo]
+        return " ".join(t for t in texts if t), [(s, toks[k]) for k, s in enumerate(segs)]
