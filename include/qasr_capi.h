@@ -999,6 +999,80 @@ typedef struct {
 } qasr_kt_segment_args;
 int qasr_kt_segment(int device, qasr_kt_segment_args *a);
 
+/* test only: the norm, RoPE and prefill / encoder attention launchers on caller-supplied arrays (csrc/kernel_harness.hip;
+ * tests/attn_util.py holds the bindings).  The conventions of qasr_kt_gemm: inputs with `guard` rows of 0xFF bytes (NaN)
+ * after their last row, outputs [rows + 2 guard][ld] pre-filled with 0xFF and returned whole, arguments validated before
+ * any launch (QASR_ERR_ARG), `declined` = 1 with `msg` where the launcher took no kernel (nothing written). */
+typedef struct {
+    int32_t kind;            /* 0 launch_layernorm_f16, 1 launch_rmsnorm_f16, 2 launch_rmsnorm_q8 */
+    int32_t M, D;
+    int32_t ldx, xrows;      /* x [xrows][ldx]; kind 0: ldx == D; xrows >= M, row_idx entries in [0, xrows) */
+    int32_t guard;
+    float eps;
+    const float *x;
+    const int32_t *row_idx;  /* kind 1: [M] or null */
+    const float *w, *b;      /* [D]; kind 0: either may be null, b unused by kinds 1 / 2 */
+    uint16_t *y;             /* kinds 0 / 1: one of y, y32 [M + 2 guard][D] */
+    float *y32;
+    int8_t *yq;              /* kind 2: [M + 2 guard][D] and yd [M + 2 guard][D / 32] */
+    float *yd;
+    int32_t declined;
+    char msg[256];
+} qasr_kt_norm_args;
+int qasr_kt_norm(int device, qasr_kt_norm_args *a);
+
+/* launch_qkv_post.  The caches are in / out between fences (qasr_kt_kv_fork): kc / vc [slots][n_kv_head][max_ctx][128],
+ * vt [slots][n_kv_head][128 * vt_ctx(max_ctx)] fp16, as the caller filled them (0xFF), back whole.  row_seq in
+ * [0, slots), row_pos in [0, min(max_ctx, max_pos)). */
+typedef struct {
+    int32_t rows, n_head, n_kv_head, max_ctx, slots, max_pos, guard;
+    float eps;
+    const float *qkv;        /* [rows][(n_head + 2 n_kv_head) * 128] */
+    const int32_t *row_seq, *row_pos;
+    const float *q_norm, *k_norm;   /* [128] */
+    const float *rope;       /* [max_pos][64][2] (cos, sin) */
+    uint16_t *q_out;         /* [rows + 2 guard][n_head * 128] */
+    float *q32, *k32;        /* both or neither: [rows + 2 guard][n_head * 128], [rows + 2 guard][n_kv_head * 128] */
+    uint16_t *kc, *vc, *vt;
+    int32_t declined;
+    char msg[256];
+} qasr_kt_qkv_post_args;
+int qasr_kt_qkv_post(int device, qasr_kt_qkv_post_args *a);
+
+/* launch_enc_attention: qkv [rows][3 D] fp32, segments [seg_start, seg_start + seg_len) inside the rows, seg_len in
+ * 1 .. max_len; D != 64 H is QASR_ERR_ARG here (the launcher throws).  One of out / out32 [rows + 2 guard][D]. */
+typedef struct {
+    int32_t rows, D, H, n_seg, max_len, f32_mfma, guard;
+    const float *qkv;
+    const int32_t *seg_start, *seg_len;
+    uint16_t *out;
+    float *out32;
+    int32_t declined;
+    char msg[256];
+} qasr_kt_enc_attention_args;
+int qasr_kt_enc_attention(int device, qasr_kt_enc_attention_args *a);
+
+/* launch_prefill_attention (exact 0) or launch_prefill_attention_exact (exact 1).  q fp16 [rows][n_head * 128]; kc / vc
+ * [slots][n_kv_head][max_ctx][128] fp16, uploaded with kKvPadRows (kernels.h) rows of 0xFF (fp16 NaN) after the last
+ * region -- the exact kernel stages V up to 127 rows past a sequence's last key -- between fences, and verified
+ * unchanged after the launch.  Sequence s: rows seq_row0[s] .. + seq_len[s] - 1 (1 .. max_len of them), cache slot
+ * seq_slot[s], keys 0 .. seq_pos0[s] + seq_len[s] - 1 <= max_ctx - 1.  q32 / k32 (exact only, both, without seq_pos0):
+ * fp32 [rows][n_head * 128] / [rows][n_kv_head * 128].  One of out / out32 [rows + 2 guard][n_head * 128]. */
+typedef struct {
+    int32_t exact, rows, n_head, n_kv_head, max_ctx, slots, n_seq, max_len, guard;
+    float scale;
+    const uint16_t *q;
+    const uint16_t *kc, *vc;
+    const int32_t *seq_row0, *seq_len, *seq_slot;
+    const int32_t *seq_pos0; /* or null */
+    const float *q32, *k32;  /* or null */
+    uint16_t *out;
+    float *out32;
+    int32_t declined;
+    char msg[256];
+} qasr_kt_prefill_attention_args;
+int qasr_kt_prefill_attention(int device, qasr_kt_prefill_attention_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -603,6 +603,8 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(PrefillAttnArgs a) {
 
 void launch_prefill_attention(const PrefillAttnArgs &a, hipStream_t s) {
     if (a.n_seq <= 0 || a.max_len <= 0) return;
+    // (the kernel's workgroup is one kv head's two query heads: head = gk * 2 + ...)
+    if (a.n_head != 2 * a.n_kv_head) return note_declined_shape("launch_prefill_attention", a.max_len, a.n_head, a.n_kv_head);
     dim3 grid((a.max_len + 31) / 32, a.n_kv_head, a.n_seq);
     hipLaunchKernelGGL(prefill_attn_kernel, grid, dim3(256), 0, s, a);
 }

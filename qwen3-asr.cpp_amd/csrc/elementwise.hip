@@ -154,6 +154,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
 void launch_layernorm_f16(const float *x, int M, int D, const float *w, const float *b, float eps, uint16_t *y, hipStream_t s,
                           float *y32) {
     if (M <= 0) return;
+    // (the <2048> instance holds any narrower row; a wider one it would normalise over its first 2048 columns)
+    if (D <= 0 || D > 2048) return note_declined_shape("launch_layernorm_f16", M, D, D);
     dim3 grid((M + 3) / 4);
     switch (D) {
         case 896: hipLaunchKernelGGL(layernorm_kernel<896>, grid, dim3(256), 0, s, x, M, w, b, eps, y, y32); break;
@@ -184,9 +186,11 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float *__restrict__ 
     rms_row<D>(v, w, eps, row, y, y32, yq, yd);
 }
 
-static void rmsnorm_any(const float *x, int ldx, const int *row_idx, int M, int D, const float *w, float eps, uint16_t *y,
-                        float *y32, int8_t *yq, float *yd, hipStream_t s) {
+static void rmsnorm_any(const char *what, const float *x, int ldx, const int *row_idx, int M, int D, const float *w, float eps,
+                        uint16_t *y, float *y32, int8_t *yq, float *yd, hipStream_t s) {
     if (M <= 0) return;
+    // (a row is D / 256 unguarded 16-B loads a lane: the instance must match D, the rows must be 16-B aligned)
+    if ((D != 256 && D != 1024 && D != 2048) || ldx % 4 != 0) return note_declined_shape(what, M, D, ldx);
     dim3 grid((M + 3) / 4);
     switch (D) {
         case 1024: hipLaunchKernelGGL(rmsnorm_kernel<1024>, grid, dim3(256), 0, s, x, ldx, row_idx, M, w, eps, y, y32, yq, yd); break;
@@ -197,11 +201,11 @@ static void rmsnorm_any(const float *x, int ldx, const int *row_idx, int M, int 
 
 void launch_rmsnorm_f16(const float *x, int ldx, const int *row_idx, int M, int D, const float *w, float eps, uint16_t *y,
                         hipStream_t s, float *y32) {
-    rmsnorm_any(x, ldx, row_idx, M, D, w, eps, y, y32, nullptr, nullptr, s);
+    rmsnorm_any("launch_rmsnorm_f16", x, ldx, row_idx, M, D, w, eps, y, y32, nullptr, nullptr, s);
 }
 
 void launch_rmsnorm_q8(const float *x, int ldx, int M, int D, const float *w, float eps, int8_t *yq, float *yd, hipStream_t s) {
-    rmsnorm_any(x, ldx, nullptr, M, D, w, eps, nullptr, nullptr, yq, yd, s);
+    rmsnorm_any("launch_rmsnorm_q8", x, ldx, nullptr, M, D, w, eps, nullptr, nullptr, yq, yd, s);
 }
 
 // --------------------------------------------------------- embedding/splice

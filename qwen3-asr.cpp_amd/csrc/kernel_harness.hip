@@ -1,7 +1,8 @@
 // kernel_harness.hip -- test-only C entry points (include/qasr_capi.h, "test
 // only"): one GEMM / GEMV / quantisation launcher of kernels.h on arrays the
 // caller supplies, so tests/test_gpu_kernels.py can hold every tile, tiling and
-// epilogue to a float64 reference without a model.
+// epilogue to a float64 reference without a model; likewise the norm, RoPE and
+// prefill / encoder attention launchers for tests/test_gpu_attn_kernels.py.
 //
 // What a kernel may not touch is made visible: inputs carry `guard` rows of
 // 0xFF bytes (NaN) after their last row (0x7F for int8 quants), outputs are
@@ -629,5 +630,158 @@ extern "C" int qasr_kt_segment(int device, qasr_kt_segment_args *a) {
         if ((rc = get(e[l], he[l])) || (rc = get(s[l], hs[l])) || (rc = get(peak[l], hpk[l])) || (rc = get(prec[l], hpr[l])) ||
             (rc = get(cuts[l], hc[l])) || (rc = get(nseg[l], hn[l])))
             return rc;
+    return 0;
+}
+
+// ------------------------------------------- norms, RoPE, prefill / encoder attention
+// (tests/test_gpu_attn_kernels.py; the launchers return nothing, so "declined" is take_declined's word)
+namespace {
+template <class Args>
+int finish_declinable(Args *a) {
+    std::string msg;
+    const bool declined = take_declined(&msg);
+    const int rc = finish_plain(&a->declined, !declined);
+    copy_str(a->msg, sizeof a->msg, msg);
+    return rc;
+}
+}  // namespace
+
+extern "C" int qasr_kt_norm(int device, qasr_kt_norm_args *a) {
+    if (!a || a->kind < 0 || a->kind > 2 || a->M <= 0 || a->D <= 0 || a->guard < 0 || !a->x || a->xrows < a->M || a->ldx < a->D)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    if (a->kind == 0 ? (a->ldx != a->D || a->row_idx || !a->y == !a->y32 || a->yq || a->yd)
+                     : (!a->w || (a->kind == 1 ? (!a->y == !a->y32 || a->yq || a->yd)
+                                               : (a->row_idx || a->y || a->y32 || !a->yq || !a->yd || a->D % 32 != 0))))
+        return fail(QASR_ERR_ARG, "operands missing or not this launcher's");
+    if (a->row_idx)
+        for (int i = 0; i < a->M; i++)
+            if (a->row_idx[i] < 0 || a->row_idx[i] >= a->xrows) return fail(QASR_ERR_ARG, "row_idx outside [0, xrows)");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int M = a->M, D = a->D, G = a->guard;
+    KtBuf x, idx, w, b, y, y32, yq, yd;
+    if ((rc = put_in(x, a->x, a->xrows, a->ldx, 4, G, 0xFF)) || (rc = put_in(idx, a->row_idx, 1, M, 4, 0, 0)) ||
+        (rc = put_in(w, a->w, 1, D, 4, 1, 0xFF)) || (rc = put_in(b, a->b, 1, D, 4, 1, 0xFF)) || (rc = put_out(y, a->y, M, D, 2, G)) ||
+        (rc = put_out(y32, a->y32, M, D, 4, G)) || (rc = put_out(yq, a->yq, M, D, 1, G)) || (rc = put_out(yd, a->yd, M, D / 32, 4, G)))
+        return rc;
+    switch (a->kind) {
+        case 0: launch_layernorm_f16(x.ptr<float>(), M, D, w.ptr<float>(), b.ptr<float>(), a->eps, y.ptr<uint16_t>(), nullptr, y32.ptr<float>()); break;
+        case 1:
+            launch_rmsnorm_f16(x.ptr<float>(), a->ldx, idx.ptr<int>(), M, D, w.ptr<float>(), a->eps, y.ptr<uint16_t>(), nullptr,
+                               y32.ptr<float>());
+            break;
+        default: launch_rmsnorm_q8(x.ptr<float>(), a->ldx, M, D, w.ptr<float>(), a->eps, yq.ptr<int8_t>(), yd.ptr<float>(), nullptr); break;
+    }
+    if ((rc = finish_declinable(a))) return rc;
+    if ((rc = get(y, a->y)) || (rc = get(y32, a->y32)) || (rc = get(yq, a->yq)) || (rc = get(yd, a->yd))) return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_qkv_post(int device, qasr_kt_qkv_post_args *a) {
+    if (!a || a->rows <= 0 || a->n_head <= 0 || a->n_kv_head <= 0 || a->max_ctx <= 0 || a->slots <= 0 || a->max_pos <= 0 || a->guard < 0 ||
+        !a->qkv || !a->row_seq || !a->row_pos || !a->q_norm || !a->k_norm || !a->rope || !a->q_out || !a->kc || !a->vc || !a->vt ||
+        !a->q32 != !a->k32)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    for (int r = 0; r < a->rows; r++)
+        if (a->row_seq[r] < 0 || a->row_seq[r] >= a->slots || a->row_pos[r] < 0 || a->row_pos[r] >= std::min(a->max_ctx, a->max_pos))
+            return fail(QASR_ERR_ARG, "row_seq / row_pos outside the caches or the rope table");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int R = a->rows, G = a->guard, QD = a->n_head * 128, KD = a->n_kv_head * 128;
+    const size_t kv = (size_t)a->slots * a->n_kv_head * a->max_ctx * 128 * 2, vt = (size_t)a->slots * a->n_kv_head * 128 * vt_ctx(a->max_ctx) * 2;
+    KtBuf qkv, seq, pos, qn, kn, rope, qo, q32, k32;
+    KtFenced kc, vc, vtb;
+    if ((rc = put_in(qkv, a->qkv, R, QD + 2 * KD, 4, G, 0xFF)) || (rc = put_in(seq, a->row_seq, 1, R, 4, 0, 0)) ||
+        (rc = put_in(pos, a->row_pos, 1, R, 4, 0, 0)) || (rc = put_in(qn, a->q_norm, 1, 128, 4, 1, 0xFF)) ||
+        (rc = put_in(kn, a->k_norm, 1, 128, 4, 1, 0xFF)) || (rc = put_in(rope, a->rope, a->max_pos, 128, 4, G, 0xFF)) ||
+        (rc = put_out(qo, a->q_out, R, QD, 2, G)) || (rc = put_out(q32, a->q32, R, QD, 4, G)) || (rc = put_out(k32, a->k32, R, KD, 4, G)) ||
+        (rc = kc.put(a->kc, kv)) || (rc = vc.put(a->vc, kv)) || (rc = vtb.put(a->vt, vt)))
+        return rc;
+    QkvPostArgs p{};
+    p.qkv = qkv.ptr<float>(); p.rows = R;
+    p.row_seq = seq.ptr<int>(); p.row_pos = pos.ptr<int>();
+    p.q_norm = qn.ptr<float>(); p.k_norm = kn.ptr<float>(); p.eps = a->eps;
+    p.rope = rope.ptr<float>();
+    p.n_head = a->n_head; p.n_kv_head = a->n_kv_head;
+    p.q_out = qo.ptr<uint16_t>();
+    p.kc = kc.b.ptr<uint16_t>(); p.vc = vc.b.ptr<uint16_t>(); p.vt = vtb.b.ptr<uint16_t>();
+    p.max_ctx = a->max_ctx;
+    p.q32 = q32.ptr<float>(); p.k32 = k32.ptr<float>();
+    launch_qkv_post(p, nullptr);
+    if ((rc = finish_declinable(a))) return rc;
+    if ((rc = get(qo, a->q_out)) || (rc = get(q32, a->q32)) || (rc = get(k32, a->k32)) || (rc = kc.take(a->kc, "kc")) ||
+        (rc = vc.take(a->vc, "vc")) || (rc = vtb.take(a->vt, "vt")))
+        return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_enc_attention(int device, qasr_kt_enc_attention_args *a) {
+    if (!a || a->rows <= 0 || a->D <= 0 || a->H <= 0 || a->n_seg <= 0 || a->max_len <= 0 || a->guard < 0 || !a->qkv || !a->seg_start ||
+        !a->seg_len || !a->out == !a->out32)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    if (a->D != 64 * a->H) return fail(QASR_ERR_ARG, "encoder attention: D must be 64 H");   // (the launcher throws)
+    for (int i = 0; i < a->n_seg; i++)
+        if (a->seg_start[i] < 0 || a->seg_len[i] < 1 || a->seg_len[i] > a->max_len || a->seg_start[i] > a->rows - a->seg_len[i])
+            return fail(QASR_ERR_ARG, "a segment outside the rows or longer than max_len");
+    int rc = use_device(device);
+    if (rc) return rc;
+    KtBuf qkv, st, ln, out, out32;
+    if ((rc = put_in(qkv, a->qkv, a->rows, 3 * a->D, 4, a->guard, 0xFF)) || (rc = put_in(st, a->seg_start, 1, a->n_seg, 4, 0, 0)) ||
+        (rc = put_in(ln, a->seg_len, 1, a->n_seg, 4, 0, 0)) || (rc = put_out(out, a->out, a->rows, a->D, 2, a->guard)) ||
+        (rc = put_out(out32, a->out32, a->rows, a->D, 4, a->guard)))
+        return rc;
+    try {
+        launch_enc_attention(qkv.ptr<float>(), st.ptr<int>(), ln.ptr<int>(), a->n_seg, a->max_len, a->D, a->H, out.ptr<uint16_t>(), nullptr,
+                             out32.ptr<float>(), a->f32_mfma != 0);
+    } catch (const std::exception &e) {
+        return fail(QASR_ERR_ARG, e.what());
+    }
+    if ((rc = finish_declinable(a))) return rc;
+    if ((rc = get(out, a->out)) || (rc = get(out32, a->out32))) return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_prefill_attention(int device, qasr_kt_prefill_attention_args *a) {
+    if (!a || a->rows <= 0 || a->n_head <= 0 || a->n_kv_head <= 0 || a->n_head % a->n_kv_head != 0 || a->max_ctx <= 0 || a->slots <= 0 ||
+        a->n_seq <= 0 || a->max_len <= 0 || a->guard < 0 || !a->q || !a->kc || !a->vc || !a->seq_row0 || !a->seq_len || !a->seq_slot ||
+        !a->out == !a->out32 || !a->q32 != !a->k32 || (a->q32 && (!a->exact || a->seq_pos0)))
+        return fail(QASR_ERR_ARG, "bad arguments");
+    for (int s = 0; s < a->n_seq; s++) {
+        const int L = a->seq_len[s], P0 = a->seq_pos0 ? a->seq_pos0[s] : 0;
+        if (L < 1 || L > a->max_len || a->seq_row0[s] < 0 || a->seq_row0[s] > a->rows - L || a->seq_slot[s] < 0 || a->seq_slot[s] >= a->slots ||
+            P0 < 0 || P0 > a->max_ctx - L)
+            return fail(QASR_ERR_ARG, "a sequence outside the rows, the slots or the context");
+    }
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int G = a->guard, QD = a->n_head * 128, KD = a->n_kv_head * 128;
+    // the caches as a context holds them: the regions, then kKvPadRows rows the exact kernel may stage (NaN here)
+    const size_t kv = (size_t)a->slots * a->n_kv_head * a->max_ctx * 128 * 2, padded = kv + (size_t)kKvPadRows * 128 * 2;
+    std::vector<unsigned char> hk(padded, 0xFF), hv(padded, 0xFF), bk(padded), bv(padded);
+    memcpy(hk.data(), a->kc, kv);
+    memcpy(hv.data(), a->vc, kv);
+    KtBuf q, r0, ln, sl, p0, q32, k32, out, out32;
+    KtFenced kc, vc;
+    if ((rc = put_in(q, a->q, a->rows, QD, 2, G, 0xFF)) || (rc = put_in(r0, a->seq_row0, 1, a->n_seq, 4, 0, 0)) ||
+        (rc = put_in(ln, a->seq_len, 1, a->n_seq, 4, 0, 0)) || (rc = put_in(sl, a->seq_slot, 1, a->n_seq, 4, 0, 0)) ||
+        (rc = put_in(p0, a->seq_pos0, 1, a->n_seq, 4, 0, 0)) || (rc = put_in(q32, a->q32, a->rows, QD, 4, G, 0xFF)) ||
+        (rc = put_in(k32, a->k32, a->rows, KD, 4, G, 0xFF)) || (rc = put_out(out, a->out, a->rows, QD, 2, G)) ||
+        (rc = put_out(out32, a->out32, a->rows, QD, 4, G)) || (rc = kc.put(hk.data(), padded)) || (rc = vc.put(hv.data(), padded)))
+        return rc;
+    PrefillAttnArgs p{};
+    p.q = q.ptr<uint16_t>();
+    p.kc = kc.b.ptr<uint16_t>(); p.vc = vc.b.ptr<uint16_t>();
+    p.seq_row0 = r0.ptr<int>(); p.seq_len = ln.ptr<int>(); p.seq_slot = sl.ptr<int>(); p.n_seq = a->n_seq; p.max_len = a->max_len;
+    p.n_head = a->n_head; p.n_kv_head = a->n_kv_head; p.max_ctx = a->max_ctx;
+    p.scale = a->scale;
+    p.out = out.ptr<uint16_t>(); p.out32 = out32.ptr<float>();
+    p.q32 = q32.ptr<float>(); p.k32 = k32.ptr<float>();
+    p.seq_pos0 = p0.ptr<int>();
+    if (a->exact) launch_prefill_attention_exact(p, nullptr);
+    else launch_prefill_attention(p, nullptr);
+    if ((rc = finish_declinable(a))) return rc;
+    if ((rc = kc.take(bk.data(), "kc")) || (rc = vc.take(bv.data(), "vc"))) return rc;
+    if (bk != hk || bv != hv) return fail(QASR_ERR_STATE, "a write into the K / V cache");
+    if ((rc = get(out, a->out)) || (rc = get(out32, a->out32))) return rc;
     return 0;
 }

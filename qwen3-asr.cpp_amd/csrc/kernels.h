@@ -328,6 +328,10 @@ bool launch_ffn1(const GemvArgs &gu, const GemvArgs &dn, unsigned int *cnt, unsi
                  hipStream_t s, bool dry = false);
 
 // ---------------------------------------------------------------- norms
+// Shapes the launchers below take (anything else is declined through note_declined_shape, nothing launched):
+//   launch_layernorm_f16        1 <= D <= 2048 (rows D apart)
+//   launch_rmsnorm_f16 / _q8    D in {256, 1024, 2048}, ldx % 4 == 0 (16-B row loads); w non-null
+//   launch_prefill_attention    n_head == 2 * n_kv_head (launch_prefill_attention_exact: any whole ratio)
 // LayerNorm (ggml_norm + mul + add) fp32 [M][D] -> fp16 y, or fp32 y32 when
 // non-null (input of a Q8_0 layer)
 void launch_layernorm_f16(const float *x, int M, int D, const float *w, const float *b, float eps, uint16_t *y, hipStream_t s,

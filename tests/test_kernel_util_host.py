@@ -220,3 +220,153 @@ def test_rms_prologue_tie_mask():
     mid = np.array([1.0 + s / 2, (1.0 + s / 2) * (1 + 2.0 ** -18)])
     frac = np.mod(mid / ku.ulp16(mid), 1.0)
     assert list(np.abs(frac - 0.5) * ku.ulp16(mid) <= 2.0 ** -20 * mid) == [True, False]
+
+
+# ------------------------------------------------- tests/attn_util.py: norms, RoPE, attention
+# On the inputs of the smallest GPU case of each family (tests/test_gpu_attn_kernels.py): the reference itself is
+# accepted, the reference with one planted defect is rejected.
+import attn_util as au   # noqa: E402
+
+
+def _enc_small(f32_mfma):
+    case = au.enc_case(1)
+    return (case,) + au.enc_reference(case, f32_mfma)
+
+
+@pytest.mark.parametrize("f32_mfma", [False, True])
+@pytest.mark.parametrize("fp16", [False, True])
+def test_enc_attention_defects_are_rejected(f32_mfma, fp16):
+    case, ref, bound, valid = _enc_small(f32_mfma)
+    assert au.check_rows(au.fake_output(ref, valid, fp16), valid, ref, bound, fp16, "clean") <= 1.0
+    starts, lens = case["seg_start"], case["seg_len"]
+
+    def drop_tile_last(i):   # the last key of the first 64-key tile
+        own = np.arange(starts[i], starts[i] + lens[i])
+        return np.delete(own, 63) if lens[i] >= 64 else own
+
+    def neighbour(i):        # the segment before's last row (the first segment: the next one's first row)
+        own = np.arange(starts[i], starts[i] + lens[i])
+        other = starts[i] - 2 if starts[i] >= 2 else starts[i] + lens[i] + 1
+        return np.append(own, other)
+    for keys_of in (drop_tile_last, neighbour):
+        bad = au.enc_reference(case, f32_mfma, keys_of)[0]
+        with pytest.raises(AssertionError, match="outside the bound"):
+            au.check_rows(au.fake_output(bad, valid, fp16), valid, ref, bound, fp16, keys_of.__name__)
+    # a row between two segments written, a segment's element left unwritten
+    buf = au.fake_output(ref, valid, fp16)
+    buf.view(np.uint16 if fp16 else np.uint32)[au.GUARD + int(np.argwhere(~valid)[0, 0]), 3] = 0
+    with pytest.raises(AssertionError, match="outside every segment"):
+        au.check_rows(buf, valid, ref, bound, fp16, "gap")
+    buf = au.fake_output(ref, valid, fp16)
+    buf.view(np.uint16 if fp16 else np.uint32)[au.GUARD + int(np.argwhere(valid)[-1, 0]), 63] = 0xFFFF if fp16 else 0xFFFFFFFF
+    with pytest.raises(AssertionError, match="never written"):
+        au.check_rows(buf, valid, ref, bound, fp16, "hole")
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+def test_prefill_causal_limit_off_by_one_after_a_cached_prefix_is_rejected(fp16):
+    case = au.prefill_case(2, 1, au.PREFILL_CACHED, 11, False)
+    valid = au.prefill_valid(case)
+    ref, bound = au.prefill_reference(case)
+    assert au.check_rows(au.fake_output(ref, valid, fp16), valid, ref, bound, fp16, "clean") <= 1.0
+    for kw in (dict(limit_shift=1), dict(limit_shift=-1), dict(drop_key=63)):
+        bad = au.prefill_reference(case, **kw)[0]
+        with pytest.raises(AssertionError, match="outside the bound"):
+            au.check_rows(au.fake_output(bad, valid, fp16), valid, ref, bound, fp16, str(kw))
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+def test_exact_chain_defects_are_rejected(fp16):
+    case = au.prefill_case(2, 1, au.PREFILL_CACHED, au.EXACT_SEED_CACHED, True)
+    chain = au.exact_chain(case)
+    valid = au.prefill_valid(case)
+    ratio, share = au.check_exact(au.fake_output(chain[0], valid, fp16), case, chain, fp16, "clean")
+    assert ratio <= 1.0 and 0 < share <= 0.05
+    for kw in (dict(limit_shift=1), dict(limit_shift=-1), dict(drop_key=63)):
+        bad = au.exact_chain(case, **kw)[0]
+        with pytest.raises(AssertionError, match="outside the bound"):
+            au.check_exact(au.fake_output(bad, valid, fp16), case, chain, fp16, str(kw))
+    # one fp16 ulp of the accumulator on an element that is no near-tie (fp32 output: the chain's own bits)
+    if not fp16:
+        ref, tie, step, rel = chain
+        r, c = np.argwhere(valid[:, None] & ~tie & (np.abs(ref) > 0.05))[7]
+        bad = ref.copy()
+        bad[r, c] += step[r, c]
+        with pytest.raises(AssertionError, match="outside the bound"):
+            au.check_exact(au.fake_output(bad, valid, False), case, chain, False, "one ulp")
+    # a case whose elements are mostly near-ties no longer tests the chain's bits
+    with pytest.raises(AssertionError, match="near-ties"):
+        au.check_exact(au.fake_output(chain[0], valid, fp16), case, (chain[0], np.ones_like(chain[1]), chain[2], chain[3]), fp16, "cap")
+
+
+def test_qkv_post_defects_are_rejected():
+    case = au.qkv_case(2, 1, 3)
+    q, bq, k, bk, v = au.qkv_post_ref(case)
+    q_bad, _, k_bad, _, _ = au.qkv_post_ref(case, pair_adjacent=True)   # the rotation's pair (i, i + 64) taken as (i, i + 1)
+    assert ku.check_values(q.astype(np.float32), q, bq) <= 1.0
+    assert ku.check_values(q.astype(np.float32).astype(np.float16).view(np.uint16), q, bq, fp16=True) <= 1.0
+    for fp16 in (False, True):
+        for good, bad, bound in ((q, q_bad, bq), (k, k_bad, bk)):
+            out = bad.astype(np.float32)
+            with pytest.raises(AssertionError, match="outside the bound"):
+                ku.check_values(out.astype(np.float16).view(np.uint16) if fp16 else out, good, bound, fp16=fp16)
+    # the caches: a row at a neighbouring position, two keys swapped inside a V^T 8-key block
+    want = au.vt_expected(case, v)
+    au.check_vt(want.copy(), want)
+    n = 128 * au.vt_ctx(case["max_ctx"])
+    d = np.arange(128)
+    assert (case["row_seq"][0], case["row_pos"][0]) == (2, 7)
+    base = (2 * case["n_kv_head"] + 0) * n
+    bad = want.copy()
+    bad[base + au.vt_index(7, d)], bad[base + au.vt_index(6, d)] = want[base + au.vt_index(6, d)], want[base + au.vt_index(7, d)]
+    with pytest.raises(AssertionError, match="vt:"):
+        au.check_vt(bad, want)
+    cache = np.full((case["slots"], case["n_kv_head"], case["max_ctx"], 128), 0xFFFF, np.uint16)
+    cache[case["row_seq"], :, case["row_pos"]] = k.astype(np.float32).astype(np.float16).view(np.uint16).reshape(3, 1, 128)
+    assert au.check_cache_rows(cache.reshape(-1), case, k, bk, "kc") <= 1.0
+    moved = cache.copy()
+    moved[2, :, 6], moved[2, :, 7] = cache[2, :, 7], cache[2, :, 6]
+    with pytest.raises(AssertionError, match="outside"):
+        au.check_cache_rows(moved.reshape(-1), case, k, bk, "kc")
+
+
+def test_layernorm_one_pass_variance_is_rejected():
+    rng = np.random.default_rng([256, 1])
+    D = 256
+    w = (1 + 0.2 * rng.standard_normal(D)).astype(np.float32)
+    b = rng.standard_normal(D).astype(np.float32)
+    x = au.norm_rows(rng, 5, D)   # row 1: mean 50 x its spread
+    ref, bound = au.layernorm_ref(x, w, b, 1e-5)
+    assert ku.check_values(ref.astype(np.float32), ref, bound) <= 1.0
+    bad = au.layernorm_one_pass(x, w, b, 1e-5)
+    assert np.abs(bad[0] - ref[0]).max() < 1e-5   # an ordinary row hides it
+    with pytest.raises(AssertionError, match="outside the bound"):
+        ku.check_values(bad[1:2], ref[1:2], bound[1:2])
+    # RMSNorm: the restatement's bits, and one fp16 ulp off outside the near-tie mask
+    xr = au.norm_rows(rng, 5, D)
+    h, v, tie = ku.rms_prologue(xr, w, 1e-6)
+    assert au.check_rms_bits(h.view(np.uint16), xr, w, 1e-6) <= 0.01
+    r, c = np.argwhere(~tie & (np.abs(v) > 0.1))[0]
+    off = h.copy()
+    off[r, c] = ku._f16_from_index(ku._f16_index(h[r:r + 1, c:c + 1]) + 1)[0, 0]
+    with pytest.raises(AssertionError, match="restatement"):
+        au.check_rms_bits(off.view(np.uint16), xr, w, 1e-6)
+
+
+def test_exact_chain_mask_covers_an_expf_one_ulp_off(monkeypatch):
+    """what the near-tie mask is for: a device expf within 1 ulp of the restatement's may change marked elements
+    only, and those by no more than their slack"""
+    case = au.prefill_case(2, 1, au.PREFILL_CACHED, au.EXACT_SEED_CACHED, True)
+    chain = au.exact_chain(case)
+    valid = au.prefill_valid(case)
+    exact = au._expf
+    for step in (np.inf, -np.inf):
+        def off_by_one(x, step=step):
+            y = exact(x)
+            return np.where(np.asarray(x) == 0, y, np.nextafter(y, np.float32(step))).astype(np.float32)   # (expf(0) is 1 anywhere)
+        monkeypatch.setattr(au, "_expf", off_by_one)
+        dev = au.exact_chain(case)[0]
+        monkeypatch.setattr(au, "_expf", exact)
+        moved = np.abs(dev - chain[0]) > 1e-12 * np.abs(chain[0])
+        assert moved[valid].any() and not (moved & ~chain[1])[valid].any()
+        assert au.check_exact(au.fake_output(dev, valid, False), case, chain, False, "expf off by one")[0] <= 1.0
