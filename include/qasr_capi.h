@@ -1073,6 +1073,41 @@ typedef struct {
 } qasr_kt_prefill_attention_args;
 int qasr_kt_prefill_attention(int device, qasr_kt_prefill_attention_args *a);
 
+/* The decode attention launchers that do not wait in-launch (never the fused batch-1 launch: qcnt, gran, sgran,
+ * att_done, trace, stamp and err are always null).  mode 0: launch_decode_attention; 1: the same in scores mode,
+ * scores [B * n_head + 2 guard][max_ctx] out (masked positions keep the sentinel); 2: the scores launch, then
+ * launch_decode_attention_exact; 3: launch_decode_attention_exact_seq (false -> declined); 4: the chain alone,
+ * launch_decode_attention_exact on scores_in [B * n_head][max_ctx] (any whole n_head / n_kv_head; qkv, norms, rope,
+ * kc and vc unused and may be null).
+ * Row b is cache slot b: kc / vc [B][n_kv_head][max_ctx][128] (uploaded with kKvPadRows rows of 0xFF after the last
+ * region), vt [B][n_kv_head][128 * vt_ctx(max_ctx)] fp16, in / out between fences.  part is sized from
+ * decode_max_splits() and counter [B][n_kv_head] is zero on entry, both between fences; a counter that is not zero
+ * again after a launch is QASR_ERR_STATE.  repeat 2 (modes 0, 2, 3): a second launch on the same part and counter,
+ * the caches restored in between (and required equal after both), into the *_b outputs.
+ * Before any launch (QASR_ERR_ARG): 0 <= pos[b] < min(max_ctx, max_pos); grid_splits * 64 > max pos; the launch's
+ * split count <= decode_max_splits(); exactly one of out / out32 / outq + outd (mode 1: scores instead)
+ * [B + 2 guard][n_head * 128] (outd: [..][n_head * 4]).
+ * tag: the kernels taken, e.g. "decode_split<64>", "decode_seq<0>+decode_exact<1>". */
+typedef struct {
+    int32_t mode, B, n_head, n_kv_head, max_ctx, max_pos, grid_splits, spl1, spl_batch, stream_blocks, kv_nt, fx_seq, repeat, guard;
+    float scale, eps;
+    const int32_t *pos;      /* [B] */
+    const float *qkv;        /* [B][(n_head + 2 n_kv_head) * 128] */
+    const float *q_norm, *k_norm;   /* [128] */
+    const float *rope;       /* [max_pos][64][2] (cos, sin) */
+    const float *scores_in;  /* mode 4 */
+    uint16_t *kc, *vc, *vt;
+    float *scores;           /* mode 1 */
+    uint16_t *out, *out_b;
+    float *out32, *out32_b;
+    int8_t *outq, *outq_b;
+    float *outd, *outd_b;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_decode_attention_args;
+int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_args *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1868,27 +1868,31 @@ int launch_qkv_attention1(const GemvArgs &q, const DecodeAttnArgs &a, const Gemv
     return with_o2 ? 2 : 1;
 }
 
+// keys per split of the launch launch_decode_attention makes of a (0: the per-sequence kernel, no splits)
+static int decode_split_keys(const DecodeAttnArgs &a) {
+    if (a.B <= 8) return split1(a.spl1, a.grid_splits);
+    // batches that give every CU a sequence or more: one workgroup per (kv group, sequence)
+    if (a.stream_blocks > 0 && a.n_kv_head * a.B >= a.stream_blocks / 2) return 0;
+    return a.spl_batch == 128 ? 128 : 256;   // batches: longer splits (fewer workgroups and partials per sequence)
+}
+int decode_split_count(const DecodeAttnArgs &a) {
+    const int spl = decode_split_keys(a);
+    return spl ? (int)(((long)a.grid_splits * DSPLIT + spl - 1) / spl) : 0;
+}
+
 void launch_decode_attention(const DecodeAttnArgs &a, hipStream_t s) {
     if (a.B <= 0) return;
-    if (a.B <= 8) {
-        if (split1(a.spl1, a.grid_splits) == 128) {
-            const int g2 = (a.grid_splits * DSPLIT + 127) / 128;
-            hipLaunchKernelGGL(decode_attn_kernel<128>, dim3(g2, a.n_kv_head, a.B), dim3(256), 0, s, a);
-        } else {
-            hipLaunchKernelGGL(decode_attn_kernel<DSPLIT>, dim3(a.grid_splits, a.n_kv_head, a.B), dim3(256), 0, s, a);
-        }
-    } else if (a.stream_blocks > 0 && a.n_head == 2 * a.n_kv_head && a.n_kv_head * a.B >= a.stream_blocks / 2) {
-        // batches that give every CU a sequence or more: one workgroup per (kv group, sequence)
-        hipLaunchKernelGGL(decode_attn_seq_kernel<0>, dim3(a.n_kv_head, a.B), dim3(256), 0, s, a);
-    } else {   // batches: longer splits (fewer workgroups and partials per sequence)
-        if (a.spl_batch == 128) {
-            const int g2 = (a.grid_splits * DSPLIT + 127) / 128;
-            hipLaunchKernelGGL(decode_attn_kernel<128>, dim3(g2, a.n_kv_head, a.B), dim3(256), 0, s, a);
-        } else {
-            const int g4 = (a.grid_splits * DSPLIT + 255) / 256;
-            hipLaunchKernelGGL(decode_attn_kernel<256>, dim3(g4, a.n_kv_head, a.B), dim3(256), 0, s, a);
-        }
-    }
+    // (kernels.h, above DecodeAttnArgs: two query heads a kv group; a split count the part rows hold)
+    const int spl = decode_split_keys(a), nsp = decode_split_count(a);
+    if (a.n_head != 2 * a.n_kv_head || (spl && (nsp < 1 || (!a.scores && nsp > a.max_splits))))
+        return note_declined_shape("launch_decode_attention", a.n_head, a.n_kv_head, a.grid_splits);
+    const dim3 grid(nsp, a.n_kv_head, a.B);
+    if (spl == 0) hipLaunchKernelGGL(decode_attn_seq_kernel<0>, dim3(a.n_kv_head, a.B), dim3(256), 0, s, a);
+    else if (spl == DSPLIT) hipLaunchKernelGGL(decode_attn_kernel<DSPLIT>, grid, dim3(256), 0, s, a);
+    else if (spl == 128) hipLaunchKernelGGL(decode_attn_kernel<128>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(decode_attn_kernel<256>, grid, dim3(256), 0, s, a);
+    if (spl) note_kernel("decode_split", 1, spl);
+    else note_kernel("decode_seq", 1, 0);
 }
 
 // the one-launch exact attention of a decode batch where the per-sequence
@@ -1900,6 +1904,7 @@ bool launch_decode_attention_exact_seq(const DecodeAttnArgs &a, hipStream_t s) {
         lds > 32768)
         return false;
     hipLaunchKernelGGL(decode_attn_seq_kernel<1>, dim3(a.n_kv_head, a.B), dim3(256), lds, s, a);
+    note_kernel("decode_seq", 1, 1);
     return true;
 }
 

@@ -409,11 +409,13 @@ __global__ __launch_bounds__(256) void decode_attn_exact_pair_kernel(DecodeAttnA
 
 void launch_decode_attention_exact(const DecodeAttnArgs &a, hipStream_t s) {
     if (a.B <= 0) return;
+    if (a.n_kv_head <= 0 || a.n_head % a.n_kv_head != 0)   // (kernels.h, above DecodeAttnArgs: whole kv groups)
+        return note_declined_shape("launch_decode_attention_exact", a.n_head, a.n_kv_head, a.max_ctx);
     // (measured on configs[2], Q8_0 64 x 30 s: decode 285.7 -> 267.2 ms, tools/experiments.sh fxpair)
-    if (a.n_head % 2 == 0 && (a.n_head / a.n_kv_head) % 2 == 0)
-        hipLaunchKernelGGL(decode_attn_exact_pair_kernel, dim3(a.n_head / 2, a.B), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(decode_attn_exact_kernel, dim3(a.n_head, a.B), dim3(128), 0, s, a);
+    const bool pair = a.n_head % 2 == 0 && (a.n_head / a.n_kv_head) % 2 == 0;
+    if (pair) hipLaunchKernelGGL(decode_attn_exact_pair_kernel, dim3(a.n_head / 2, a.B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(decode_attn_exact_kernel, dim3(a.n_head, a.B), dim3(128), 0, s, a);
+    note_kernel("decode_exact", 1, pair ? 1 : 0);
 }
 
 }  // namespace qasr

@@ -2,7 +2,9 @@
 // only"): one GEMM / GEMV / quantisation launcher of kernels.h on arrays the
 // caller supplies, so tests/test_gpu_kernels.py can hold every tile, tiling and
 // epilogue to a float64 reference without a model; likewise the norm, RoPE and
-// prefill / encoder attention launchers for tests/test_gpu_attn_kernels.py.
+// prefill / encoder attention launchers for tests/test_gpu_attn_kernels.py, and
+// the decode attention launchers that do not wait in-launch for
+// tests/test_gpu_decode_attn_kernels.py.
 //
 // What a kernel may not touch is made visible: inputs carry `guard` rows of
 // 0xFF bytes (NaN) after their last row (0x7F for int8 quants), outputs are
@@ -783,5 +785,140 @@ extern "C" int qasr_kt_prefill_attention(int device, qasr_kt_prefill_attention_a
     if ((rc = kc.take(bk.data(), "kc")) || (rc = vc.take(bv.data(), "vc"))) return rc;
     if (bk != hk || bv != hv) return fail(QASR_ERR_STATE, "a write into the K / V cache");
     if ((rc = get(out, a->out)) || (rc = get(out32, a->out32))) return rc;
+    return 0;
+}
+
+// ------------------------------------------------------------ decode attention
+// (tests/test_gpu_decode_attn_kernels.py) the launchers that do not wait in-launch: the fused batch-1 launch's
+// counters, granules, trace, stamp and error word are always null here
+extern "C" int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_args *a) {
+    if (!a || a->mode < 0 || a->mode > 4 || a->B <= 0 || a->n_head <= 0 || a->n_kv_head <= 0 || a->max_ctx <= 0 || a->max_pos <= 0 ||
+        a->guard < 0 || a->repeat < 1 || a->repeat > 2 || !a->pos || !a->vt)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const int mode = a->mode, B = a->B, G = a->guard, nh = a->n_head, nkv = a->n_kv_head;
+    const bool chain_only = mode == 4, two = a->repeat == 2;
+    if (chain_only ? !a->scores_in : !(a->qkv && a->q_norm && a->k_norm && a->rope && a->kc && a->vc))
+        return fail(QASR_ERR_ARG, "operands missing");
+    if (two && (mode == 1 || mode == 4)) return fail(QASR_ERR_ARG, "repeat 2 is for modes 0, 2 and 3");
+    const int kinds = (a->out != nullptr) + (a->out32 != nullptr) + (a->outq != nullptr);
+    if (!a->outq != !a->outd || (mode == 1 ? (kinds != 0 || !a->scores) : (kinds != 1 || a->scores)))
+        return fail(QASR_ERR_ARG, "exactly one output kind");
+    if (two && (!a->out != !a->out_b || !a->out32 != !a->out32_b || !a->outq != !a->outq_b || !a->outd != !a->outd_b))
+        return fail(QASR_ERR_ARG, "repeat 2 needs the second output of the same kind");
+    int top = 0;
+    for (int b = 0; b < B; b++) {
+        if (a->pos[b] < 0 || a->pos[b] >= std::min(a->max_ctx, a->max_pos)) return fail(QASR_ERR_ARG, "pos outside the caches or the rope table");
+        top = std::max(top, a->pos[b]);
+    }
+    if (!chain_only) {
+        if (a->grid_splits <= 0 || (long)a->grid_splits * decode_split_len() <= top)
+            return fail(QASR_ERR_ARG, "grid_splits does not cover the longest sequence");
+        DecodeAttnArgs probe{};
+        probe.B = B; probe.n_head = nh; probe.n_kv_head = nkv; probe.grid_splits = a->grid_splits; probe.spl1 = a->spl1;
+        probe.spl_batch = a->spl_batch; probe.stream_blocks = a->stream_blocks;
+        if (decode_split_count(probe) > decode_max_splits()) return fail(QASR_ERR_ARG, "more splits than decode_max_splits()");
+    }
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int QD = nh * 128, KD = nkv * 128, MS = decode_max_splits();
+    const size_t kv = (size_t)B * nkv * a->max_ctx * 128 * 2, padded = kv + (size_t)kKvPadRows * 128 * 2;
+    const size_t vtb = (size_t)B * nkv * 128 * vt_ctx(a->max_ctx) * 2;
+    const size_t part_bytes = (size_t)B * nkv * MS * 2 * 132 * 4, cnt_bytes = (size_t)B * nkv * 4;
+    std::vector<unsigned char> hk(padded, 0xFF), hv(padded, 0xFF), k1, v1, t1, k2(padded), v2(padded), hpart(part_bytes, 0xFF),
+        hcnt(cnt_bytes, 0);
+    if (!chain_only) {
+        memcpy(hk.data(), a->kc, kv);
+        memcpy(hv.data(), a->vc, kv);
+    }
+    KtBuf qkv, pos, qn, kn, rope, sc_in, sc_mid, sc_out, o16[2], o32[2], oq[2], od[2];
+    KtFenced kc, vc, vt, part, cnt;
+    uint16_t *h16[2] = {a->out, a->out_b};
+    float *h32[2] = {a->out32, a->out32_b}, *hd[2] = {a->outd, a->outd_b};
+    int8_t *hq[2] = {a->outq, a->outq_b};
+    if ((rc = put_in(qkv, a->qkv, B, QD + 2 * KD, 4, G, 0xFF)) || (rc = put_in(pos, a->pos, 1, B, 4, 0, 0)) ||
+        (rc = put_in(qn, a->q_norm, 1, 128, 4, 1, 0xFF)) || (rc = put_in(kn, a->k_norm, 1, 128, 4, 1, 0xFF)) ||
+        (rc = put_in(rope, a->rope, a->max_pos, 128, 4, G, 0xFF)) || (rc = put_in(sc_in, a->scores_in, (long)B * nh, a->max_ctx, 4, G, 0xFF)) ||
+        (rc = put_out(sc_out, a->scores, (long)B * nh, a->max_ctx, 4, G)) ||
+        // (mode 2's scores stay on the device: allocated like an output, never copied back)
+        (rc = put_out(sc_mid, mode == 2 ? (const void *)a : nullptr, (long)B * nh, a->max_ctx, 4, G)) || (rc = kc.put(hk.data(), padded)) ||
+        (rc = vc.put(hv.data(), padded)) || (rc = vt.put(a->vt, vtb)) || (rc = part.put(hpart.data(), part_bytes)) ||
+        (rc = cnt.put(hcnt.data(), cnt_bytes)))
+        return rc;
+    for (int r = 0; r < a->repeat; r++)
+        if ((rc = put_out(o16[r], h16[r], B, QD, 2, G)) || (rc = put_out(o32[r], h32[r], B, QD, 4, G)) ||
+            (rc = put_out(oq[r], hq[r], B, QD, 1, G)) || (rc = put_out(od[r], hd[r], B, QD / 32, 4, G)))
+            return rc;
+    DecodeAttnArgs d{};
+    d.qkv = qkv.ptr<float>(); d.q_norm = qn.ptr<float>(); d.k_norm = kn.ptr<float>(); d.eps = a->eps;
+    d.rope = rope.ptr<float>(); d.pos = pos.ptr<int>();
+    d.kc = kc.b.ptr<uint16_t>(); d.vc = vc.b.ptr<uint16_t>(); d.vt = vt.b.ptr<uint16_t>();
+    d.B = B; d.n_head = nh; d.n_kv_head = nkv; d.max_ctx = a->max_ctx; d.max_splits = MS; d.grid_splits = a->grid_splits;
+    d.scale = a->scale;
+    d.part = part.b.ptr<float>(); d.counter = cnt.b.ptr<unsigned int>();
+    d.spl1 = a->spl1; d.spl_batch = a->spl_batch; d.stream_blocks = a->stream_blocks; d.kv_nt = a->kv_nt; d.fx_seq = a->fx_seq;
+    std::string tags, msg;
+    bool declined = false;
+    // one launcher call: its tag or its declined message
+    auto after = [&](bool ran) {
+        std::string t, m;
+        const bool dec = take_declined(&m) || !ran;
+        const bool tagged = take_kernel(&t);
+        if (dec) {
+            declined = true;
+            msg = m.empty() ? "the launcher returned false" : m;
+            return 0;
+        }
+        if (!tagged) return fail(QASR_ERR_STATE, "the launcher recorded no kernel tag");
+        tags += (tags.empty() ? "" : "+") + t;
+        return 0;
+    };
+    for (int r = 0; r < a->repeat && !declined; r++) {
+        if (r) {   // the caches as the caller gave them; part and counter as the first launch left them
+            k1.resize(padded); v1.resize(padded); t1.resize(vtb);
+            if ((rc = kc.take(k1.data(), "kc")) || (rc = vc.take(v1.data(), "vc")) || (rc = vt.take(t1.data(), "vt"))) return rc;
+            HIPCHK(hipMemcpy(kc.b.ptr<char>(), hk.data(), padded, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(vc.b.ptr<char>(), hv.data(), padded, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(vt.b.ptr<char>(), a->vt, vtb, hipMemcpyHostToDevice));
+            tags.clear();
+        }
+        d.out = o16[r].ptr<uint16_t>(); d.out32 = o32[r].ptr<float>(); d.outq = oq[r].ptr<int8_t>(); d.outd = od[r].ptr<float>();
+        d.scores = nullptr;
+        switch (mode) {
+            case 0: launch_decode_attention(d, nullptr); rc = after(true); break;
+            case 1: d.scores = sc_out.ptr<float>(); launch_decode_attention(d, nullptr); rc = after(true); break;
+            case 2:
+                d.scores = sc_mid.ptr<float>();
+                launch_decode_attention(d, nullptr);
+                if ((rc = after(true)) || declined) break;
+                launch_decode_attention_exact(d, nullptr);
+                rc = after(true);
+                break;
+            case 3: rc = after(launch_decode_attention_exact_seq(d, nullptr)); break;
+            default: d.scores = sc_in.ptr<float>(); launch_decode_attention_exact(d, nullptr); rc = after(true); break;
+        }
+        if (rc) return rc;
+        int32_t unused = 0;
+        if ((rc = finish_plain(&unused, true))) return rc;
+        std::vector<unsigned char> c(cnt_bytes);
+        if ((rc = cnt.take(c.data(), "the split counters"))) return rc;
+        if (c != hcnt) return fail(QASR_ERR_STATE, "a split counter is not zero after the launch");
+    }
+    a->declined = declined;
+    copy_str(a->tag, sizeof a->tag, declined ? std::string() : tags);
+    copy_str(a->msg, sizeof a->msg, msg);
+    if ((rc = part.take(hpart.data(), "part")) || (rc = kc.take(k2.data(), "kc")) || (rc = vc.take(v2.data(), "vc")) ||
+        (rc = vt.take(a->vt, "vt")))
+        return rc;
+    if (memcmp(k2.data() + kv, hk.data() + kv, padded - kv) || memcmp(v2.data() + kv, hv.data() + kv, padded - kv))
+        return fail(QASR_ERR_STATE, "a write into the rows after the last K / V region");
+    if (two && !declined && (k1 != k2 || v1 != v2 || memcmp(t1.data(), a->vt, vtb)))
+        return fail(QASR_ERR_STATE, "the two launches left different caches");
+    if (!chain_only) {
+        memcpy(a->kc, k2.data(), kv);
+        memcpy(a->vc, v2.data(), kv);
+    }
+    if ((rc = get(sc_out, a->scores))) return rc;
+    for (int r = 0; r < a->repeat; r++)
+        if ((rc = get(o16[r], h16[r])) || (rc = get(o32[r], h32[r])) || (rc = get(oq[r], hq[r])) || (rc = get(od[r], hd[r]))) return rc;
     return 0;
 }

@@ -413,6 +413,20 @@ __host__ __device__ inline uint32_t gran_tag(int pos, int layer) { return ((uint
 // decoder single-token attention, fused: q/k RMSNorm + RoPE, fp16 KV-cache
 // write of the new token and split-KV flash decoding (64-key splits); the last
 // arriving split of each kv group combines the partials and writes out.
+// Shapes the decode launchers take (anything else is declined through note_declined_shape, nothing launched):
+//   launch_decode_attention            n_head == 2 * n_kv_head (the split and per-sequence kernels hold two query
+//                                      heads a kv group); a split count (decode_split_count) of 1 .. max_splits,
+//                                      the rows part holds per (sequence, kv group) (scores mode: any count >= 1)
+//   launch_decode_attention_exact      n_head % n_kv_head == 0
+//   launch_decode_attention_exact_seq  returns false outside B > 8, fx_seq, the per-sequence dispatch and
+//                                      2 * max_ctx floats of LDS <= 32 KiB
+// What the kernels read of the caches of a sequence at position pos (tests poison accordingly):
+//   K / V rows above pos are never loaded: loads clamp to kcap = min(pos, max_ctx - 1).
+//   Row pos itself is loaded as the cache holds it (stale) for the masked keys of the split or chunk and for key
+//   pos before the new row replaces it in registers; V's copy is multiplied by a zero weight, so it must be finite.
+//   V^T keys pos + 1 .. 8 (pos / 8) + 7 (the rest of pos's 8-key block) are loaded by the exact chain and
+//   multiplied by a zero weight: finite.  V^T from the next key block on is never loaded (blocks past the
+//   last re-read it).
 struct DecodeAttnArgs {
     const float *qkv;                    // [B][QD + 2*KD] fp32 (raw QKV projection)
     const float *q_norm, *k_norm; float eps;
@@ -481,6 +495,9 @@ int launch_qkv_attention1(const GemvArgs &q, const DecodeAttnArgs &a, const Gemv
                           bool dry = false);
 int decode_split_len();
 int decode_max_splits();
+// splits per (sequence, kv group) of the launch launch_decode_attention makes of a (B, n_kv_head, grid_splits, spl1,
+// spl_batch, stream_blocks); 0 = the per-sequence kernel
+int decode_split_count(const DecodeAttnArgs &a);
 
 // ---------------------------------------------------------------- decoder misc
 // embedding gather (fp16 -> fp32) + audio splice (src/text_decoder.cpp:429-459)

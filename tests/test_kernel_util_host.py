@@ -226,6 +226,7 @@ def test_rms_prologue_tie_mask():
 # On the inputs of the smallest GPU case of each family (tests/test_gpu_attn_kernels.py): the reference itself is
 # accepted, the reference with one planted defect is rejected.
 import attn_util as au   # noqa: E402
+import decode_attn_util as du   # noqa: E402
 
 
 def _enc_small(f32_mfma):
@@ -370,3 +371,90 @@ def test_exact_chain_mask_covers_an_expf_one_ulp_off(monkeypatch):
         moved = np.abs(dev - chain[0]) > 1e-12 * np.abs(chain[0])
         assert moved[valid].any() and not (moved & ~chain[1])[valid].any()
         assert au.check_exact(au.fake_output(dev, valid, False), case, chain, False, "expf off by one")[0] <= 1.0
+
+
+# ======================================================= decode attention
+DEC_POS = (0, 1, 15, 16, 31, 32, 33, 62, 64, 129)   # the smallest GPU cases' lengths: one split, a seam, three chunks
+
+
+def test_decode_lattice_family_is_exact_and_under_the_mask_cap():
+    """the float32 restatement of the norm and rotation gives the float64 reference's q and k, the fp32 score sums
+    are exact (asserted inside lattice_scores), and the restatement alone keeps its near-tie share under the cap for
+    every lattice case and seed the GPU file uses"""
+    for pos, ctx, wmax in (((0, 30, 31, 32, 62, 63, 64, 129), 320, 12), ((0, 30, 31, 32, 62, 63, 64, 129, 257), 320, 12),
+                           ((2046, 2047), 2112, 32), ((2048, 32), 2112, 32), ((2048, 2047, 2046, 64, 63, 0, 1, 500, 1000), 2112, 32)):
+        case = du.decode_case(pos, 1, ctx, du.LATTICE_SEED, True, wmax=wmax)
+        s = du.lattice_scores(case)
+        assert np.array_equal(s[~np.isnan(s)].astype(np.float32).astype(np.float64), s[~np.isnan(s)])
+        chain = du.lattice_chain(case)
+        assert 0 < chain[1].mean() <= 0.05, (pos, chain[1].mean())
+    for rise in ("late", "early"):
+        case = du.chain_case((2048, 2047), 2, 1, 2112, du.CHAIN_SEED, rise, 4.0)
+        assert du.chain_case_reference(case)[1].mean() <= 0.05
+        s = case["scores_in"][0, :, :2049]
+        first = np.argmax(s, 1)
+        assert (first == (2048 if rise == "late" else 5)).all()   # the maximum rises in the second weights chunk / never there
+    for ratio, nkv in ((2, 1), (3, 1), (4, 2), (1, 1)):
+        case = du.chain_case((0, 30, 31, 32, 62, 63, 64), ratio, nkv, 96, du.CHAIN_SEED)
+        assert du.chain_case_reference(case)[1].mean() <= 0.05
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+@pytest.mark.parametrize("spl", [64, 0])
+def test_decode_reference_defects_are_rejected(fp16, spl):
+    case = du.decode_case(DEC_POS, 1, 320, 11)
+    gs = 3
+    ref, bound = du.decode_reference(case, spl, gs)
+    B, QD = ref.shape
+    clean = ku.in_range(du.fake(ref, fp16), B, QD)
+    assert ku.check_values(clean, ref, bound, fp16=fp16) <= 1.0
+    assert np.abs(ref).max() < 100   # the junk of row pos is nowhere in it
+    for defect in ("stale", "drop_last_split", "empty_split", "seam_twice", "next_key"):
+        bad = du.decode_reference(case, spl, gs, defect)[0]
+        with pytest.raises(AssertionError, match="outside the bound|NaN in range"):
+            ku.check_values(ku.in_range(du.fake(bad, fp16), B, QD), ref, bound, fp16=fp16, what=defect)
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+def test_decode_chain_defects_are_rejected(fp16):
+    case = du.decode_case(DEC_POS[:8] + (64, 129), 1, 320, du.LATTICE_SEED, True)
+    chain = du.lattice_chain(case)
+    ratio, share = du.check_chain(du.fake(chain[0], fp16), chain, fp16, "clean")
+    assert ratio <= 1.0 and 0 < share <= 0.05
+    bad = du.lattice_chain(case, vshift=8)[0]   # the V^T block taken as (k >> 3) + 1
+    with pytest.raises(AssertionError, match="outside the bound"):
+        du.check_chain(du.fake(bad, fp16), chain, fp16, "vt block")
+    # one fp16 ulp of the accumulator on an element that is no near-tie (fp32 output: the chain's own bits)
+    if not fp16:
+        ref, tie, step, rel = chain
+        r, c = np.argwhere(~tie & (np.abs(ref) > 0.05))[7]
+        off = ref.copy()
+        off[r, c] += step[r, c]
+        with pytest.raises(AssertionError, match="outside the bound"):
+            du.check_chain(du.fake(off, False), chain, False, "one ulp")
+    with pytest.raises(AssertionError, match="near-ties"):
+        du.check_chain(du.fake(chain[0], fp16), (chain[0], np.ones_like(chain[1]), chain[2], chain[3]), fp16, "cap")
+
+
+def test_decode_chain_missed_rescale_in_the_second_weights_chunk_is_rejected():
+    case = du.chain_case((2048, 2047), 2, 1, 2112, du.CHAIN_SEED, "late", 4.0)
+    chain = du.chain_case_reference(case)
+    assert du.check_chain(du.fake(chain[0]), chain, False, "clean")[0] <= 1.0
+    bad = du.chain_case_reference(case, skip_rescale_from=2048)[0]
+    assert np.array_equal(bad[1], chain[0][1])   # 2048 keys: one chunk, untouched
+    with pytest.raises(AssertionError, match="outside the bound"):
+        du.check_chain(du.fake(bad), chain, False, "no rescale")
+
+
+def test_decode_chain_mask_covers_an_expf_one_ulp_off():
+    case = du.decode_case(DEC_POS[:8] + (64, 129), 1, 320, du.LATTICE_SEED, True)
+    chain = du.lattice_chain(case)
+    exact = au._expf
+    for step in (np.inf, -np.inf):
+        def off_by_one(x, step=step):
+            y = exact(x)
+            return np.where(np.asarray(x) == 0, y, np.nextafter(y, np.float32(step))).astype(np.float32)   # (expf(0) is 1 anywhere)
+        dev = du.lattice_chain(case, expf=off_by_one)[0]
+        moved = np.abs(dev - chain[0]) > 1e-12 * np.abs(chain[0])
+        assert moved.any() and not (moved & ~chain[1]).any()
+        assert du.check_chain(du.fake(dev), chain, False, "expf off by one")[0] <= 1.0
