@@ -1108,6 +1108,41 @@ typedef struct {
 } qasr_kt_decode_attention_args;
 int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_args *a);
 
+/* The conv front end (tests/conv_util.py holds the bindings).  layer 1: launch_conv1 over mel; 2 / 3: launch_gemm in
+ * AM_CONV2 / AM_CONV3 with EPI_GELU_F16, N = C, K = 9 C, ldw = conv_kpad(C) = 9 C rounded up to 128, ldo16 = C,
+ * row_start taken from the chunks' row2 / row3 -- called directly, through no context.  chunks: ChunkDesc of
+ * csrc/kernels.h field for field, every field filled by the caller.
+ * The input -- mel, in_len floats (layer 1), or the activation the layer reads, [in_len][C] fp16 (act1 / act2) -- is
+ * uploaded between guard_in elements (floats / rows of C) of 0xFF bytes on both sides, so a tap that should have been
+ * padding reads NaN inside the allocation at the first and the last chunk too; the caller passes at least the widest
+ * row of the input image + 1 (mel: a clip's frames + 1).  W: layer 1 fp16 [C][9]; layers 2 / 3 fp16 [C][conv_kpad(C)],
+ * the padding columns as the caller chose them (zero where the 8-phase tile is expected: its contract; NaN
+ * elsewhere), with `guard` rows of 0xFF after it; bias [C].  out: [out_rows + 2 guard][C] fp16 as qasr_kt_gemm's.
+ * Before any launch (QASR_ERR_ARG): every chunk's reads and writes lie inside in_len / out_rows, the output rows of
+ * the chunks are consecutive from 0 and out_rows is their sum (layers 2 / 3: find_chunk's contract). */
+typedef struct {
+    int64_t mel_off;
+    int32_t T, L, Lv, W1, W2, W3, row1, row2, row3, enc_row;
+} qasr_kt_chunk;
+typedef struct {
+    int32_t layer;           /* 1, 2, 3 */
+    int32_t C, regs_staged, n_chunks;
+    int32_t in_len, out_rows;
+    int32_t guard, guard_in;
+    int32_t max_w1;          /* layer 1: the grid's width (the engine: the widest chunk's W1) */
+    const qasr_kt_chunk *chunks;
+    const float *mel;        /* layer 1 */
+    const uint16_t *act;     /* layers 2 / 3 */
+    const uint16_t *W;
+    const float *bias;
+    uint16_t *out;
+    uint16_t *gelu_out;      /* [65536] */
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_conv_args;
+int qasr_kt_conv(int device, qasr_kt_conv_args *a);
+
 #ifdef __cplusplus
 }
 #endif

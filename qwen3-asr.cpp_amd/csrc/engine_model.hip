@@ -60,7 +60,7 @@ extern "C" int qasr_model_load(const char *path, int device, qasr_model **out) {
     if (hp.head_dim != 128 || hp.n_head != 2 * hp.n_kv_head)
         return fail(QASR_ERR_FORMAT, "decoder must have head_dim 128 and GQA ratio 2");
     if (hp.n_mel != 128) return fail(QASR_ERR_FORMAT, "n_mel must be 128");
-    if (hp.conv_ch % 32 || hp.dec_ffn % 16) return fail(QASR_ERR_FORMAT, "unsupported conv/ffn width");
+    if (!conv_width_ok(hp.conv_ch) || hp.dec_ffn % 16) return fail(QASR_ERR_FORMAT, "unsupported conv/ffn width");
 
     const int C = hp.conv_ch, D = hp.d_model, FF = hp.enc_ffn, H = hp.hidden, V = hp.vocab;
     const int QD = hp.n_head * 128, KD = hp.n_kv_head * 128, F = hp.dec_ffn;

@@ -194,7 +194,12 @@ static void dispatch_tiles(const GemmArgs &g, hipStream_t s) {
             run_gemm8p<EPI, AMODE>(h, s);
             return;
         }
-        // conv: K = 9*C, slab group must stay inside one tap -> C % (32*KS) == 0
+        // conv: K = 9*C, slab group must stay inside one tap -> C % (32*KS) == 0; grid.x = N / BN
+        // covers every column only where BN divides N (kernels.h conv_gemm_width_ok states the three cases below).
+        // The check sits after the 8-phase branch on purpose: that tile computes any N % 32 == 0 whole (its last
+        // column tile is shifted back), so nothing it takes runs short; qasr_model_load refuses a width that would
+        // be computed at >= 2048 rows and declined below, so no loaded model's fate depends on its batch
+        if (!conv_gemm_width_ok(g.N, g.C)) return note_declined_shape("launch_gemm (conv)", g.M, g.N, g.K);
         if (g.N == 480) {
             // all 480 output channels per block: the gathered A tile is read once
             // (N/96 = 5 re-reads of the im2col rows otherwise), W stays L2-resident

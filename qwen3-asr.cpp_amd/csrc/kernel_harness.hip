@@ -4,10 +4,12 @@
 // epilogue to a float64 reference without a model; likewise the norm, RoPE and
 // prefill / encoder attention launchers for tests/test_gpu_attn_kernels.py, and
 // the decode attention launchers that do not wait in-launch for
-// tests/test_gpu_decode_attn_kernels.py.
+// tests/test_gpu_decode_attn_kernels.py, and the conv front end (launch_conv1,
+// launch_gemm in AM_CONV2 / AM_CONV3) for tests/test_gpu_conv_kernels.py.
 //
 // What a kernel may not touch is made visible: inputs carry `guard` rows of
-// 0xFF bytes (NaN) after their last row (0x7F for int8 quants), outputs are
+// 0xFF bytes (NaN) after their last row (0x7F for int8 quants; the conv entry's
+// input: before its first row too, where a mis-bounded tap lands), outputs are
 // allocated with `guard` rows on both sides and every byte 0xFF before the
 // launch, and come back whole.  A launcher that takes no kernel is reported
 // as declined, never as success.
@@ -921,4 +923,73 @@ extern "C" int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_arg
     for (int r = 0; r < a->repeat; r++)
         if ((rc = get(o16[r], h16[r])) || (rc = get(o32[r], h32[r])) || (rc = get(oq[r], hq[r])) || (rc = get(od[r], hd[r]))) return rc;
     return 0;
+}
+
+// ------------------------------------------------------------- conv front end
+// (tests/test_gpu_conv_kernels.py) launch_conv1 and launch_gemm's AM_CONV2 / AM_CONV3 on a caller-supplied chunk
+// table.  The input sits between guard_in elements of 0xFF bytes on both sides: the NHWC layout puts a neighbour's
+// valid data where a mis-bounded padding tap lands, and at the first and last chunk that neighbour is NaN here.
+static_assert(sizeof(qasr_kt_chunk) == sizeof(ChunkDesc) && offsetof(qasr_kt_chunk, T) == offsetof(ChunkDesc, T) &&
+                  offsetof(qasr_kt_chunk, row1) == offsetof(ChunkDesc, row1) && offsetof(qasr_kt_chunk, enc_row) == offsetof(ChunkDesc, enc_row),
+              "qasr_kt_chunk mirrors ChunkDesc");
+
+extern "C" int qasr_kt_conv(int device, qasr_kt_conv_args *a) {
+    if (!a || a->layer < 1 || a->layer > 3 || a->C <= 0 || a->n_chunks <= 0 || a->in_len <= 0 || a->out_rows <= 0 || a->guard < 0 ||
+        a->guard_in < 0 || !a->chunks || !a->W || !a->bias || !a->out || (a->layer == 1 ? !a->mel || a->max_w1 < 1 : !a->act))
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const int layer = a->layer, C = a->C, NC = a->n_chunks, G = a->guard;
+    // every address a chunk's in-bounds taps and its output rows can form lies inside the arrays; the output rows
+    // of the chunks are consecutive from 0 (find_chunk) and out_rows is their sum
+    std::vector<int> starts(NC);
+    long next = 0;
+    for (int c = 0; c < NC; c++) {
+        const qasr_kt_chunk &d = a->chunks[c];
+        if (d.W1 < 1 || d.W2 < 1 || d.W3 < 1 || d.T < 1 || d.L < 1 || d.Lv < 0 || d.Lv > d.L) return fail(QASR_ERR_ARG, "a chunk's widths");
+        const long rin = layer == 2 ? d.row1 : d.row2, nin = layer == 2 ? 64L * d.W1 : 32L * d.W2;
+        const long rout = layer == 1 ? d.row1 : layer == 2 ? d.row2 : d.row3;
+        const long nout = layer == 1 ? 64L * d.W1 : layer == 2 ? 32L * d.W2 : 16L * d.W3;
+        if (layer == 1 ? (d.mel_off < 0 || d.Lv > d.T || d.mel_off + 127L * d.T + d.Lv > a->in_len) : (rin < 0 || rin + nin > a->in_len))
+            return fail(QASR_ERR_ARG, "a chunk reads outside the input");
+        if (rout != next) return fail(QASR_ERR_ARG, "the chunks' output rows are not consecutive from 0");
+        starts[c] = (int)rout;
+        next += nout;
+    }
+    if (next != a->out_rows) return fail(QASR_ERR_ARG, "out_rows is not the sum of the chunks' rows");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int KP = layer == 1 ? 9 : conv_kpad(C);
+    // the input between two guards
+    const int esz = layer == 1 ? 4 : 2;
+    const size_t unit = (size_t)(layer == 1 ? 1 : C) * esz, lead = (size_t)a->guard_in * unit, real = (size_t)a->in_len * unit;
+    KtBuf in, W, bias, chunks, rs, gelu, out;
+    in.bytes = real + 2 * lead + 256;
+    in.off = lead;
+    HIPCHK(hipMalloc((void **)&in.d, in.bytes));
+    HIPCHK(hipMemset(in.d, 0xFF, in.bytes));
+    HIPCHK(hipMemcpy(in.d + lead, layer == 1 ? (const void *)a->mel : (const void *)a->act, real, hipMemcpyHostToDevice));
+    if ((rc = put_in(W, a->W, C, KP, 2, G, 0xFF)) || (rc = put_in(bias, a->bias, 1, C, 4, 1, 0xFF)) ||
+        (rc = put_state(chunks, a->chunks, (size_t)NC * sizeof(ChunkDesc))) || (rc = put_state(rs, starts.data(), (size_t)NC * 4)) ||
+        (rc = put_out(out, a->out, a->out_rows, C, 2, G)))
+        return rc;
+    std::vector<uint16_t> lut;
+    gelu_table(lut);
+    if ((rc = put_in(gelu, lut.data(), 1, 65536, 2, 0, 0))) return rc;
+    if (a->gelu_out) memcpy(a->gelu_out, lut.data(), 65536 * 2);
+    if (layer == 1) {
+        launch_conv1(in.ptr<float>(), chunks.ptr<ChunkDesc>(), rs.ptr<int>(), NC, a->out_rows, W.ptr<uint16_t>(), bias.ptr<float>(),
+                     gelu.ptr<uint16_t>(), C, out.ptr<uint16_t>(), nullptr, a->max_w1);
+    } else {
+        GemmArgs g{};
+        g.A = in.ptr<uint16_t>();
+        g.W = W.ptr<uint16_t>(); g.ldw = KP;
+        g.M = a->out_rows; g.N = C; g.K = 9 * C;
+        g.chunks = chunks.ptr<ChunkDesc>(); g.row_start = rs.ptr<int>(); g.n_chunks = NC; g.C = C;
+        g.bias = bias.ptr<float>();
+        g.out_f16 = out.ptr<uint16_t>(); g.ldo16 = C;
+        g.gelu = gelu.ptr<uint16_t>();
+        g.regs_staged = a->regs_staged;
+        launch_gemm(layer == 2 ? AM_CONV2 : AM_CONV3, EPI_GELU_F16, g, nullptr);
+    }
+    if ((rc = finish(a, true))) return rc;
+    return get(out, a->out);
 }

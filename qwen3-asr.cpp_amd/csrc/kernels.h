@@ -73,6 +73,19 @@ struct ChunkDesc {
     int enc_row;    // first encoder frame (= row3 / 16)
 };
 
+// Channel counts the conv launchers compute whole (anything else is declined through note_declined_shape, nothing
+// launched; qasr_model_load refuses such a model):
+//   launch_conv1               lane l of a wave holds channels 8l .. 8l + 7: C % 8 == 0, C <= 512
+//   launch_gemm, AM_CONV2 / 3  below 2048 rows a tile family must cover all N columns with its KS 32-deep slabs
+//                              inside one 3x3 tap: N == 480 (64 x 480 tiles, C % 32 == 0), N % 96 == 0 with
+//                              C % 96 == 0 (64 / 128 x 96 x 3), or N % 64 == 0 with C % 32 == 0 (64 x 64 x 1)
+inline constexpr bool conv1_width_ok(int C) { return C > 0 && C % 8 == 0 && C <= 512; }
+inline constexpr bool conv_gemm_width_ok(int N, int C) {
+    return N > 0 && C > 0 && ((N == 480 && C % 32 == 0) || (N % 96 == 0 && C % 96 == 0) || (N % 64 == 0 && C % 32 == 0));
+}
+// a model's conv width: all three layers, at every row count (N == C)
+inline constexpr bool conv_width_ok(int C) { return conv1_width_ok(C) && conv_gemm_width_ok(C, C); }
+
 // conv1 (1 -> C, 3x3, s2, p1) + bias + GELU(LUT) -> act1 NHWC fp16 [rows1][C]
 void launch_conv1(const float *mel, const ChunkDesc *chunks, const int *row1_start, int n_chunks, int rows1,
                   const uint16_t *w /*[C][9]*/, const float *b, const uint16_t *gelu, int C, uint16_t *act1, hipStream_t s,
@@ -126,6 +139,12 @@ struct GemmArgs {
 //   launch_gemm, AM_DENSE   N % 64 == 0, K % 32 == 0, lda % 8 == 0, ldw % 8 == 0
 //                           (the 8-phase tile of >= 2048 rows: N >= 256, N % 32 == 0, K % 128 == 0,
 //                           ldo / ldo16 / ldr % 4 == 0); SwiGLU: N weight rows give N / 2 columns
+//   launch_gemm, AM_CONV2   EPI_GELU_F16 only; K == 9 * C, ldw >= K, ldw % 8 == 0, C % 8 == 0 (16-byte gathers);
+//             and AM_CONV3  conv_gemm_width_ok(N, C) above (the engine: N == C, ldw == conv_kpad(C), ldo16 == C).
+//                           The 8-phase tile of >= 2048 rows: N >= 256, N % 32 == 0, ldw % 128 == 0,
+//                           ldw - K < 128, ldo16 % 4 == 0, weight columns K .. ldw - 1 zero; other tiles never
+//                           read those columns.  row_start ascending from 0, one entry a chunk
+//   launch_conv1            conv1_width_ok(C) above; w [C][9], chunks' row1 + 64 * W1 <= rows1
 //   launch_gemm_q8          N % 64 == 0, K % 32 == 0, lda % 16 == 0, ldw % 16 == 0 (int8 elements);
 //                           scales Ad [M][ldad], Wd [N][K / 32]
 //   launch_gemm_skinny      1 <= M <= 128, K % 128 == 0, lda % 8 == 0, ldw % 8 == 0; N % 16 == 0

@@ -5,6 +5,7 @@ the evidence that tests/test_gpu_kernels.py fails on such a kernel."""
 import numpy as np
 import pytest
 
+import conv_util as cu
 import kernel_util as ku
 
 G = ku.GUARD
@@ -458,3 +459,136 @@ def test_decode_chain_mask_covers_an_expf_one_ulp_off():
         moved = np.abs(dev - chain[0]) > 1e-12 * np.abs(chain[0])
         assert moved.any() and not (moved & ~chain[1]).any()
         assert du.check_chain(du.fake(dev), chain, False, "expf off by one")[0] <= 1.0
+
+
+# ================================================================ conv front end
+
+
+def _conv_table(seed):
+    """a stand-in GELU table: any injective-enough table serves an exact comparator; NaN inputs give NaN as the real one"""
+    t = np.random.default_rng(seed).integers(0, 0x7BFF, 65536).astype(np.uint16)
+    idx = np.arange(65536)
+    t[((idx & 0x7C00) == 0x7C00) & ((idx & 0x3FF) != 0)] = 0x7E00
+    return t
+
+
+def _guarded(a, g):
+    out = np.full((a.shape[0] + 2 * g,) + a.shape[1:], np.nan)
+    out[g:g + a.shape[0]] = a
+    return out
+
+
+def gather_conv(layer, chunks, act, wdev, bias, table, defect=None):
+    """conv2 / conv3 as the device computes them -- an im2col row per output row, gathered from the NHWC row table by
+    the address base + ih * Win + iw, times the packed weights -- with one planted defect.  The input sits between
+    guard rows of NaN as in the harness"""
+    Cc, Hin = act.shape[1], 64 if layer == 2 else 32
+    gin = max(c[cu.WIDTH[layer - 1]] for c in chunks) + 1
+    a = _guarded(act.astype(np.float64), gin)
+    w = wdev[:, :9 * Cc].astype(np.float64)
+    # the output-row table the chunk search reads, and each output row's chunk: the largest c with row_start[c] <= row
+    row_start = np.array([ch[cu.ROW[layer]] for ch in chunks])
+    if defect == "row_start":
+        row_start[1] += 1
+    row = np.arange(cu.total_rows(layer, chunks))
+    c = np.searchsorted(row_start, row, side="right") - 1
+    local = row - row_start[c]
+    Wout, Win = (np.array([ch[cu.WIDTH[l]] for ch in chunks])[c] for l in (layer, layer - 1))
+    base = np.array([ch[cu.ROW[layer - 1]] for ch in chunks])[c] + (1 if defect == "in_base" else 0) * (c == 1)
+    if layer == 2 or defect == "row_order":
+        oh, ow = local // Wout, local % Wout
+    else:
+        oh, ow = local % 16, local // 16
+    oy, ox = (2 * oh, 2 * ow) if defect == "origin" else (2 * oh - 1, 2 * ow - 1)
+    A = np.zeros((len(row), 9, Cc))
+    for kh in range(3):
+        for kw in range(3):
+            ih, iw = oy + kh, ox + kw
+            ok = ((ih >= 0) | (defect == "top")) & (ih < Hin) & (iw >= 0) & ((iw < Win) | (defect == "right"))
+            A[:, kh * 3 + kw] = np.where(ok[:, None], a[np.clip(base + ih * Win + iw + gin, 0, len(a) - 1)], 0.0)
+    if defect == "k_order":
+        A = A.transpose(0, 2, 1)
+    out = A.reshape(len(row), 9 * Cc) @ w.T
+    return cu.gelu_bits((out + bias[None, :].astype(np.float64)).astype(np.float32), table)
+
+
+def gather_conv1(chunks, mel, w9, bias, table, defect=None):
+    """conv1 as the device computes it (one tap per (row, t), mel[mel_off + ih * T + iw]) with one planted defect"""
+    g = max(max(c["T"], c["L"]) for c in chunks) + 1
+    h = _guarded(mel.astype(np.float16).astype(np.float64), g)
+    w64 = w9.astype(np.float64)
+    out = np.zeros((cu.total_rows(1, chunks), w9.shape[0]), np.uint16)
+    for ch in chunks:
+        local = np.arange(64 * ch["W1"])
+        oh, ow = local // ch["W1"], local % ch["W1"]
+        sd = np.zeros((len(local), w9.shape[0]))
+        for t in range(9):
+            ih, iw = 2 * oh - 1 + t // 3, 2 * ow - 1 + t % 3
+            ok = (ih >= 0) & (ih < 128) & ((iw >= 0) | (defect == "left" and ch["start"] > 0)) & (iw < (ch["L"] if defect == "lv" else ch["Lv"]))
+            tap = np.where(ok, h[np.clip(ch["mel_off"] + ih * ch["T"] + iw + g, 0, len(h) - 1)], 0.0)
+            sd = sd + tap[:, None] * w64[None, :, t]
+        cu.chunk_rows(1, ch, out)[:] = cu.gelu_bits(sd.astype(np.float32) + bias[None, :], table)
+    return out
+
+
+def _conv_compare(bits, want, what):
+    rows, Cc = want.shape
+    cu.check_exact(ku.in_range(_alloc(bits, Cc, np.uint16), rows, Cc, what), want, what)
+
+
+def test_conv1_reference_defects_are_rejected():
+    """the smallest conv1 GPU case's inputs: the device-style gather gives the reference's bits; chunk 2's left tap
+    reading the chunk before, or frames past Lv read from the mel, do not"""
+    Cc = 96
+    rng = np.random.default_rng(Cc)
+    chunks = cu.make_chunks(cu.CONV1_CLIPS)
+    mel = (rng.standard_normal(cu.mel_len(chunks)) * 0.7 + 0.3).astype(np.float32)
+    w = ku.f16_normal(rng, (Cc, 1, 3, 3), 0.5)
+    bias = rng.standard_normal(Cc).astype(np.float32)
+    table = _conv_table(1)
+    want = cu.conv1_reference(chunks, mel, w, bias, table)
+    _conv_compare(gather_conv1(chunks, mel, w.reshape(Cc, 9), bias, table), want, "clean")
+    for defect in ("left", "lv"):
+        bad = gather_conv1(chunks, mel, w.reshape(Cc, 9), bias, table, defect)
+        with pytest.raises(AssertionError, match="differ from the exact reference"):
+            _conv_compare(bad, want, defect)
+
+
+@pytest.mark.parametrize("layer", [2, 3])
+def test_conv_gemm_reference_defects_are_rejected(layer):
+    """the smallest conv2 / conv3 GPU case's lattice inputs: the device-style gather gives the reference's bits; a
+    right pad tap of an odd width read from the next image row, ih = -1 read from the rows before, a stride origin
+    of 2 o, K ordered (ic, tap), one chunk's row_start (the output-row table of the chunk search) off by one row, one
+    chunk's first input row off by one and (conv3) rows ordered (oh, ow) do not"""
+    case = next(c for c in cu.CASES if c[0] == layer)
+    Cc, chunks = case[1], cu.make_chunks(case[2])
+    assert any(c[cu.WIDTH[layer - 1]] % 2 == 1 and c[cu.WIDTH[layer - 1]] > 1 for c in chunks)
+    act, w, bias = cu.lattice_inputs(cu.case_rng(case), layer, Cc, chunks)
+    table = _conv_table(layer)
+    want = cu.lattice_expect(layer, chunks, act, w, bias, table)
+    wdev = cu.pack_weights(w, np.nan)
+    _conv_compare(gather_conv(layer, chunks, act, wdev, bias, table), want, "clean")
+    for defect in ("right", "top", "origin", "k_order", "row_start", "in_base") + (("row_order",) if layer == 3 else ()):
+        bad = gather_conv(layer, chunks, act, wdev, bias, table, defect)
+        with pytest.raises(AssertionError, match="differ from the exact reference|NaN in range"):
+            _conv_compare(bad, want, defect)
+    # the normal family's comparator on the same geometry: the clean gather is inside the bound, a right pad tap is not
+    act, w, bias = cu.normal_inputs(cu.case_rng(case), layer, Cc, chunks)
+    ref, bound = cu.normal_expect(layer, chunks, act, w, bias)
+    wdev = cu.pack_weights(w, np.nan)
+    ku.check_gelu(gather_conv(layer, chunks, act, wdev, bias, table), table, ref, bound, "clean normal")
+    with pytest.raises(AssertionError, match="outside the table set"):
+        ku.check_gelu(gather_conv(layer, chunks, act, wdev, bias, table, "right"), table, ref, bound, "right normal")
+
+
+def test_conv_lattice_is_exact_for_every_gpu_case():
+    for case in cu.CASES:
+        layer, Cc, lengths = case[:3]
+        act, w, bias = cu.lattice_inputs(cu.case_rng(case), layer, Cc, cu.make_chunks(lengths))
+        assert cu.lattice_exact(act, w, bias) < 2 ** 14
+    # the weight packing against its statement, element by element
+    w = ku.f16_normal(np.random.default_rng(3), (8, 16, 3, 3))
+    p = cu.pack_weights(w, np.nan)
+    assert p.shape == (8, 256) and np.isnan(p[:, 144:]).all()
+    for oc, ic, kh, kw in ((0, 0, 0, 0), (7, 15, 2, 2), (3, 5, 1, 2), (4, 9, 2, 0)):
+        assert p[oc, (kh * 3 + kw) * 16 + ic] == w[oc, ic, kh, kw]
