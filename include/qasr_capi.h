@@ -524,7 +524,10 @@ int qasr_write_wav(const char *path, const float *pcm, int n, int sample_rate);
 /* deterministic synthetic clip: seed 1000+i recipe */
 int qasr_synth_pcm(uint64_t seed, int n_samples, float *out);
 /* synthetic GGUF with the reference tensor names/shapes/dtypes.
- * config: "full" (Qwen3-ASR-0.6B dims) or "tiny" (test dims);
+ * config: "full" (Qwen3-ASR-0.6B dims), "full-1.7b" (Qwen3-ASR-1.7B dims: decoder
+ * 28 x 2048, FFN 6144, the aligner's 24 x 1024 encoder), "tiny" (test dims),
+ * "tiny-ffn6144" ("tiny" with a 6144-wide decoder FFN: the smallest model whose
+ * batch <= 8 step runs the K-split GEMV), "aligner" or "aligner-tiny";
  * wtype: 1 = f16, 8 = q8_0 for linear weights. */
 int qasr_write_synthetic_gguf(const char *path, const char *config, uint64_t seed, int wtype);
 /* version of that writer's output: bumped whenever the file it writes for a
@@ -606,6 +609,8 @@ typedef struct {
     char msg[256];
 } qasr_kt_gemv_args;
 int qasr_kt_gemv(int device, qasr_kt_gemv_args *a);
+/* the same arrays, guards and reporting through launch_gemv_wide (f16 W, 4096 < K <= 8192) */
+int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a);
 
 typedef struct {
     int32_t M, K, ldx, gather_C, guard;

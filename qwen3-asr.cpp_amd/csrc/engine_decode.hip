@@ -23,6 +23,13 @@ static void dec_gemm(qasr_ctx *c, int epi, GemmArgs g, hipStream_t s) {
     launch_gemm(AM_DENSE, epi, g, s);
 }
 
+// batch <= 8 o / down projections: f16 rows longer than launch_gemv takes (the 6144-wide down projection of a
+// hidden-2048 decoder) on the K-split GEMV (gemv_wide.hip), everything else on launch_gemv as before
+static void dec_gemv(const GemvArgs &g, hipStream_t s) {
+    if (g.Wd || g.K <= 4096) return launch_gemv(EPI_F32, g, s);
+    if (!launch_gemv_wide(EPI_F32, g, s)) note_declined_shape("launch_gemv_wide", g.M, g.N, g.K);
+}
+
 // Launch groups of one decode step, in stream order (decoder cut at nl layers):
 //   0          embedding gather (batches; batch <= 8 fuses it into layer 0)
 //   1 + 2l     layer l: QKV projection + attention (+ o-projection when fused)
@@ -192,11 +199,11 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         }
         if (!gb) continue;
         if (skinny) {
-            if (!o_fused && !(skip & 4)) launch_gemv(EPI_F32, o, s);
+            if (!o_fused && !(skip & 4)) dec_gemv(o, s);
             if (o_fused) dn.zero8 = att_done;   // re-arm the fused o-proj's arrival counters
             if (skip & 24 || nl < 2 || !launch_ffn1(gu, dn, fcnt, fcnt_next, c->fuse, s)) {
                 if (!(skip & 8)) launch_gemv(q8 ? EPI_SWIGLU_F32 : EPI_SWIGLU_F16, gu, s);
-                if (!(skip & 16)) launch_gemv(EPI_F32, dn, s);
+                if (!(skip & 16)) dec_gemv(dn, s);
                 else if (o_fused) (void)hipMemsetAsync(att_done, 0, 8 * 16 * 4, s);   // the skipped down-proj re-arms these
             }
         } else if (q8) {

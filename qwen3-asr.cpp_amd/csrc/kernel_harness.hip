@@ -160,7 +160,8 @@ extern "C" int qasr_kt_gemm(int device, qasr_kt_gemm_args *a) {
     return 0;
 }
 
-extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) {
+// launch_gemv (wide = false) or launch_gemv_wide on the same arrays, guards and reporting
+static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
     if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || a->wrows < a->N)
         return fail(QASR_ERR_ARG, "bad arguments");
     if (!(a->Wq ? a->Wd != nullptr : a->W != nullptr) || !(a->x || a->xh || (a->embd_ids && a->embd)))
@@ -200,17 +201,22 @@ extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) {
     g.done = done.ptr<unsigned int>(); g.tok_out = tok.ptr<int32_t>(); g.hist = hist.ptr<int32_t>();
     g.hist_stride = a->hist_stride; g.step = step.ptr<int>(); g.pos = pos.ptr<int>();
 
+    bool ran = true;
     for (int i = 0; i < a->launches; i++) {
-        launch_gemv(a->epi, g, nullptr);
+        if (wide) ran = launch_gemv_wide(a->epi, g, nullptr) && ran;
+        else launch_gemv(a->epi, g, nullptr);
         if (i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
     }
-    if ((rc = finish(a, true))) return rc;
+    if ((rc = finish(a, ran))) return rc;
     if ((rc = get(xs, a->x_store)) || (rc = get(o32, a->out_f32)) || (rc = get(o16, a->out_f16)) || (rc = get(amax, a->amax)) ||
         (rc = get(done, a->done)) || (rc = get(tok, a->tok_out)) || (rc = get(hist, a->hist)) || (rc = get(step, a->step)) ||
         (rc = get(pos, a->pos)))
         return rc;
     return 0;
 }
+
+extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, false); }
+extern "C" int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, true); }
 
 extern "C" int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a) {
     if (!a || a->M <= 0 || a->K <= 0 || a->K % 32 != 0 || a->guard < 0 || !a->q || !a->d || !a->x32 == !a->x16 || a->gather_C < 0)

@@ -154,6 +154,9 @@ struct GemmArgs {
 //   launch_gemv, f16 W      1 <= M <= 8, K % 8 == 0, K <= 4096, ldx % 4 == 0 (x) or ldxh % 8 == 0 (xh);
 //                           W rows K apart; SwiGLU: N % 16 == 0 (whole 16-row gate / up groups)
 //   launch_gemv, Q8_0 W     1 <= M <= 8, K % 32 == 0, K <= 8192, ldx % 4 == 0; SwiGLU: N % 16 == 0
+//   launch_gemv_wide        f16 W rows K apart, 1 <= M <= 8, K in {6144, 8192} (4096 < K <= 8192, K % 2048 == 0),
+//                           xh (ldxh % 8 == 0) or x (ldx % 4 == 0); EPI_F32 (+ bias, + res, out_f32 may be res)
+//                           and EPI_F16 (+ bias); no Wd / norm_w / embd_ids / amax   -- returns false otherwise
 void launch_gemm(int amode, int epi, const GemmArgs &g, hipStream_t s);
 // an unsupported (mode, epilogue) pair or shape launches nothing and is recorded
 // for the calling host thread; take_declined returns (and clears) it -- the
@@ -252,6 +255,9 @@ bool launch_lmhead_batch(const GemvArgs &g, hipStream_t s);
 int lmhead_grid();
 // gemv.hip: one-row f16 fast path of launch_gemv (false = not covered)
 bool launch_gemv1(int epi, const GemvArgs &g, hipStream_t s);
+// gemv_wide.hip: the rows launch_gemv does not take (f16, 4096 < K <= 8192): a workgroup's four waves
+// split K and add their partial sums in wave order; false = shape not taken, nothing launched
+bool launch_gemv_wide(int epi, const GemvArgs &g, hipStream_t s);
 
 // Batch-1 fused launches (a role waits in-launch on another role's output):
 // per-context switches, delays and the device's co-residency capacity.  Every

@@ -597,11 +597,15 @@ bool write_synthetic_gguf(const std::string &path, const std::string &config, ui
     // (src/forced_aligner.h:36-73: 24 x 1024 encoder, 16 heads, ffn 4096,
     // vocab 152064, 5000-class head)
     const bool al = config == "aligner" || config == "aligner-tiny";
-    const bool tiny = config == "tiny" || config == "aligner-tiny";
-    if (!tiny && config != "full" && config != "aligner") {
+    // "full-1.7b": Qwen3-ASR-1.7B's published shapes (decoder 28 x 2048, 16 / 8 heads of 128, FFN 6144; the
+    // aligner's 24 x 1024 encoder projecting to 2048); "tiny-ffn6144": "tiny" with that FFN width
+    const bool wide = config == "tiny-ffn6144", big = config == "full-1.7b";
+    const bool tiny = config == "tiny" || config == "aligner-tiny" || wide;
+    if (!tiny && !big && config != "full" && config != "aligner") {
         err = "unknown synthetic config: " + config;
         return false;
     }
+    if (big) { hp.enc_layers = 24; hp.d_model = 1024; hp.enc_heads = 16; hp.enc_ffn = 4096; hp.hidden = 2048; hp.dec_ffn = 6144; }
     if (al) {
         hp.aligner = true;
         hp.classify_num = 5000;
@@ -609,13 +613,15 @@ bool write_synthetic_gguf(const std::string &path, const std::string &config, ui
     }
     if (tiny) {
         hp.enc_layers = 2; hp.d_model = 256; hp.enc_heads = 4; hp.enc_ffn = 512; hp.conv_ch = 96;
-        hp.hidden = 256; hp.dec_layers = 2; hp.n_head = 4; hp.n_kv_head = 2; hp.head_dim = 128; hp.dec_ffn = 512;
+        hp.hidden = 256; hp.dec_layers = 2; hp.n_head = 4; hp.n_kv_head = 2; hp.head_dim = 128; hp.dec_ffn = wide ? 6144 : 512;
     }
     if (wtype != 1 && wtype != 8) { err = "wtype must be 1 (f16) or 8 (q8_0)"; return false; }
     GGUFWriter w;
     w.add_str("general.architecture", "qwen3-asr");
     w.add_str("general.name", al ? (tiny ? "Qwen3-ForcedAligner-synthetic-tiny" : "Qwen3-ForcedAligner-0.6B-synthetic")
-                                 : (tiny ? "Qwen3-ASR-synthetic-tiny" : "Qwen3-ASR-0.6B-synthetic"));
+                                 : (wide ? "Qwen3-ASR-synthetic-tiny-ffn6144"
+                                         : tiny ? "Qwen3-ASR-synthetic-tiny"
+                                                : big ? "Qwen3-ASR-1.7B-synthetic" : "Qwen3-ASR-0.6B-synthetic"));
     w.add_u32("general.alignment", 32);
     w.add_u32("qwen3-asr.block_count", hp.dec_layers);
     w.add_u32("qwen3-asr.embedding_length", hp.hidden);

@@ -106,7 +106,7 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --file-list <path>     Text file with one audio path per line (added to the -f files)\n");
     fprintf(stderr, "  --devices <i,j,...>    Shard the audio files over these HIP devices (one replica each)\n");
     fprintf(stderr, "  --batch <n>            KV-cache slots per GPU (continuous batching) with --devices / several files (default: 16)\n");
-    fprintf(stderr, "  --synthetic <cfg>      Write a synthetic GGUF (tiny|full|aligner|aligner-tiny) to --model and exit\n");
+    fprintf(stderr, "  --synthetic <cfg>      Write a synthetic GGUF (tiny|tiny-ffn6144|full|full-1.7b|aligner|aligner-tiny) to --model and exit\n");
     fprintf(stderr, "\nForced Alignment:\n");
     fprintf(stderr, "  --align                Enable forced alignment mode\n");
     fprintf(stderr, "  --text <text>          Reference transcript for alignment\n");

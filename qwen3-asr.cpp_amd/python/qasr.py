@@ -298,6 +298,8 @@ def synth_pcm(seed: int, n: int) -> np.ndarray:
 
 
 def write_synthetic_gguf(path: str, config: str = "tiny", seed: int = 42, wtype: int = 1) -> None:
+    """config: "tiny", "tiny-ffn6144" ("tiny" with a 6144-wide decoder FFN), "full" (Qwen3-ASR-0.6B shapes),
+    "full-1.7b" (Qwen3-ASR-1.7B shapes, a multi-GB file), "aligner", "aligner-tiny"; wtype 1 = f16, 8 = q8_0."""
     _check(lib().qasr_write_synthetic_gguf(path.encode(), config.encode(), seed, wtype), "write_synthetic_gguf")
 
 
