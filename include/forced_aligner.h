@@ -19,6 +19,9 @@ struct aligned_word {
     std::string word;
     float start;   // seconds
     float end;     // seconds
+    // MI355X addition, filled with ForcedAligner::set_monotone(true): the model's log-probability of each boundary
+    float start_logprob = 0.0f;
+    float end_logprob = 0.0f;
 };
 
 struct alignment_result {
@@ -68,6 +71,10 @@ public:
     // MI355X addition (default off): align(audio_path) takes a file at any rate the resampler supports
     // (qasr_resample of qasr_capi.h) and resamples it to 16 kHz on the device; off, such a file is an error
     void set_resample(bool on) { resample_ = on; }
+    // MI355X addition (default off): timestamps from the maximum-score non-decreasing class path over the model's
+    // logits, found on the device (qasr_align_path of qasr_capi.h), in place of the per-row arg-max and its LIS
+    // repair; every word then carries the log-probabilities of its boundaries
+    void set_monotone(bool on) { monotone_ = on; }
 
 private:
     bool ensure_ctx(int n_ctx);
@@ -75,7 +82,7 @@ private:
     qasr_model *model_ = nullptr;
     qasr_ctx *ctx_ = nullptr;
     int ctx_len_ = 0, device_ = 0;
-    bool resample_ = false;
+    bool resample_ = false, monotone_ = false;
     forced_aligner_hparams hparams_;
     std::string error_msg_;
 };

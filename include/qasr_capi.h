@@ -509,6 +509,38 @@ int qasr_align_json(qasr_ctx *c, const float *pcm, int n_samples, const char *te
 int qasr_align_json_batch(qasr_ctx *c, const float *const *pcm, const int *n_samples, const char *const *text, int B,
                           const char *language, char *out, int cap, qasr_timings *t);
 
+/* ---- forced alignment: the monotone path with log-probabilities ---------
+ * Timestamps that are non-decreasing by construction and optimal under the model, and a
+ * confidence for each: the maximum-score non-decreasing class path over the classify head's
+ * fp32 logits, found on the device.  The rule (csrc/align_path_host.h states it in full), for a
+ * clip's NT timestamp rows with logits z[i][c] and C allowed classes,
+ *   C = min(classify_num, n_samples / (16 * timestamp_segment_time_ms) + 2):
+ *   dp[0][c] = z[0][c]; dp[i][c] = z[i][c] + max_{c' <= c} dp[i-1][c'] (one fp32 add), the
+ *   backpointer the SMALLEST c' attaining the maximum; the path ends at the smallest class
+ *   attaining max_c dp[NT-1][c] and follows the backpointers; score = that maximum;
+ *   logprob[i] = z[i][path[i]] - logsumexp(z[i][0 .. classify_num)).
+ * path and score are exact functions of the logits; the log-sum-exp is fp32 with the row maximum
+ * subtracted.  Option "align_monotone" (0 / 1, default 0): qasr_align_json and
+ * qasr_align_json_batch take the path instead of the arg-max classes and their LIS repair, and
+ * every word gains "start_logprob" and "end_logprob" (%.4f); at 0 nothing changes.
+ *   qasr_align_path       B clips in one aligner pass, whatever the option says.  classes,
+ *                         logprobs: [B][cap] (row b: clip b's n_ts[b] values, at most cap
+ *                         written); score [B]; each may be NULL.  A model with classify_num >
+ *                         8192 is QASR_ERR_ARG.  After it qasr_debug_read(c, "align_logits")
+ *                         reads the fp32 logits [sum n_ts][classify_num rounded up to 64].
+ *   qasr_align_path_host  the rule on the CPU (no device is touched): logits [NT][ld]; classes,
+ *                         logprobs [NT], score [1] (each may be NULL).  QASR_ERR_ARG unless
+ *                         NT >= 0 and 1 <= C <= classify_num <= ld.
+ *   qasr_align_path_last_us  device time of the last monotone pass's extra work on this context,
+ *                         microseconds, by HIP events: us[0] the fp32 classify GEMM, us[1] the
+ *                         path kernel, us[2] the row kernel.  QASR_ERR_STATE before one. */
+int qasr_align_path(qasr_ctx *c, const float *const *pcm, const int *n_samples, const int32_t *const *text_ids,
+                    const int *n_text, int B, int32_t *classes, float *logprobs, float *score, int cap, int *n_ts,
+                    qasr_timings *t);
+int qasr_align_path_host(const float *logits, int64_t ld, int NT, int classify_num, int C, int32_t *classes,
+                         float *logprobs, float *score);
+int qasr_align_path_last_us(qasr_ctx *c, int *us);
+
 /* ---- text (host) ---------------------------------------------------------- */
 /* UTF-8 text for ids (special <|..|> and [PAD..] tokens skipped); returns the
  * byte length (excluding NUL), writes at most cap-1 bytes + NUL. */
@@ -1147,6 +1179,24 @@ typedef struct {
     char msg[256];
 } qasr_kt_conv_args;
 int qasr_kt_conv(int device, qasr_kt_conv_args *a);
+
+/* test only: launch_align_path (csrc/align_path.hip) on B clips whose rows follow each other in logits
+ * [sum NT][ld] (followed by `guard` rows of 0xFF bytes).  Every output sits between `guard` elements of 0xFF
+ * bytes and comes back whole: path, logprob, lse [guard + sum NT + guard], score [guard + B + guard].
+ * launches 2: a second launch on the same inputs into the *2 outputs.  declined: the launcher took no kernel
+ * (nothing was written); bt_rows receives the backpointer rows of one LDS block of the walk back at max C. */
+typedef struct {
+    int32_t B, guard, launches, classify_num;
+    int64_t ld;
+    const int32_t *NT, *C;   /* [B] */
+    const float *logits;
+    int32_t *path, *path2;
+    float *logprob, *lse, *score, *logprob2, *lse2, *score2;
+    int32_t bt_rows, declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_align_path_args;
+int qasr_kt_align_path(int device, qasr_kt_align_path_args *a);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,7 @@ static const std::vector<FuseOption> &fuse_options() {
         {"lmh_topk", "QASR_LMH_TOPK", &FuseCfg::lmh_topk},
         {"beam_width", "QASR_BEAM_WIDTH", &FuseCfg::beam_width},
         {"sample_slices", "QASR_SAMPLE_SLICES", &FuseCfg::sample_slices},
+        {"align_monotone", "QASR_ALIGN_MONOTONE", &FuseCfg::align_monotone},
     };
     return v;
 }
@@ -369,6 +370,7 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
             if (n == "poll_limit" && value <= 0) return fail(QASR_ERR_ARG, "poll_limit must be positive");
             if (n == "top_k" && (value < 0 || value > QASR_TOPK_MAX)) return fail(QASR_ERR_ARG, "top_k out of range (0..8)");
             if (n == "beam_width" && (value < 0 || value > QASR_BEAM_MAX)) return fail(QASR_ERR_ARG, "beam_width out of range (0..8)");
+            if (n == "align_monotone" && value != 0 && value != 1) return fail(QASR_ERR_ARG, "align_monotone is 0 or 1");
             if (n == "sample_slices" && value < 0) return fail(QASR_ERR_ARG, "sample_slices must be >= 0");
             if (n == "beam_width" && value >= 2) {
                 HIPCHK(hipSetDevice(c->m->device));
@@ -432,6 +434,7 @@ extern "C" int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64
     else if (n == "act") { src = c->d_act; cap = B * hp.dec_ffn * 2; }
     else if (n == "qkv") { src = c->d_qkv; cap = B * (QD + 2 * KD) * 4; }
     else if (n == "att") { src = c->d_att; cap = B * QD * 2; }
+    else if (n == "align_logits") { src = c->alz.p; cap = c->alz_rows * c->m->cls_rows * 4; }   // the last monotone pass's
     else return fail(QASR_ERR_ARG, "unknown buffer '" + n + "'");
     if (bytes > cap) return fail(QASR_ERR_ARG, "read past the buffer");
     HIPCHK(hipSetDevice(c->m->device));

@@ -16,13 +16,23 @@ using namespace qasr::eng;
 // prompts (prefill_layers' sequences), one classify GEMM over every timestamp
 // row of every clip.  Rows are independent in each of them, so a clip's
 // classes are the same alone or in a batch (tests/test_gpu_aligner.py).
+// mono: the classes are the monotone path over the head's fp32 logits instead of each row's
+// arg-max -- the classify GEMM writes the logits of every timestamp row into c->alz, launch_align_path runs one
+// workgroup a clip over them, and the path, one log-probability a row and one score a clip come back in one copy.
+struct AlignMono {
+    std::vector<std::vector<float>> logprob;   // per clip, per timestamp row
+    std::vector<float> score;                  // per clip (0 for a clip without timestamp rows)
+};
 static int align_classes(qasr_ctx *c, const float *const *pcm, const int *n, const std::vector<std::vector<int32_t>> &text_ids,
-                         std::vector<std::vector<int32_t>> &classes, qasr_timings *t) {
+                         std::vector<std::vector<int32_t>> &classes, qasr_timings *t, AlignMono *mono = nullptr) {
     qasr_model *m = c->m;
     const Hparams &hp = m->hp;
     const int B = (int)text_ids.size();
     if (!hp.aligner || !m->cls_w) return fail(QASR_ERR_STATE, "not a ForcedAligner model");
     if (B <= 0 || B > c->max_batch) return fail(QASR_ERR_ARG, "aligner batch exceeds the context's max_batch");
+    if (mono && hp.classify_num > kAlignPathMaxC)
+        return fail(QASR_ERR_ARG, "the monotone path takes at most " + std::to_string(kAlignPathMaxC) + " classes, the model has " +
+                                      std::to_string(hp.classify_num));
     HIPCHK(hipSetDevice(m->device));
     HIPCHK(hipStreamSynchronize(c->st));
     c->pin_used = 0;
@@ -56,7 +66,47 @@ static int align_classes(qasr_ctx *c, const float *const *pcm, const int *n, con
     if ((rc = prefill_layers(c, ids, P, c->feats.as<float>(), ap, Nb, nullptr))) return rc;
     const int NT = (int)rows.size(), H = hp.hidden;
     std::vector<unsigned long long> keys(NT);
-    if (NT > 0) {
+    std::vector<char> mout;   // mono: path [NT] int32 | logprob [NT] float | score [B] float
+    if (mono) {
+        c->al_timed = false;
+        c->alz_rows = 0;
+    }
+    if (NT > 0 && mono) {
+        const long ldz = m->cls_rows;
+        std::vector<AlignClip> clips(B);
+        for (int b = 0; b < B; b++) {
+            clips[b].NT = nrows[b];
+            clips[b].C = align_path_classes(hp.classify_num, n[b], hp.ts_segment_ms);
+        }
+        const long bp_elems = align_path_layout(clips.data(), B);
+        mout.resize((size_t)NT * 8 + (size_t)B * 4);
+        if ((rc = upload(c, c->ats, rows)) || (rc = ensure(c, c->atx, (size_t)NT * H * 2)) ||
+            (rc = ensure(c, c->alz, (size_t)NT * ldz * 4)) || (rc = ensure(c, c->albp, (size_t)std::max(bp_elems, 8L) * 2)) ||
+            (rc = ensure(c, c->alout, mout.size())) || (rc = upload(c, c->alclips, clips)))
+            return rc;
+        for (auto &e : c->al_ev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        launch_rmsnorm_f16(c->px.as<float>(), H, c->ats.as<int>(), NT, H, m->out_norm, hp.rms_eps, c->atx.as<uint16_t>(), s);
+        HIPCHK(hipEventRecord(c->al_ev[0], s));
+        GemmArgs g{};
+        g.A = c->atx.as<uint16_t>(); g.lda = H; g.W = m->cls_w; g.ldw = H; g.M = NT; g.N = m->cls_rows; g.K = H;
+        g.out_f32 = c->alz.as<float>(); g.ldo = (int)ldz;
+        launch_gemm_c(c, AM_DENSE, EPI_F32, g, s);
+        HIPCHK(hipEventRecord(c->al_ev[1], s));
+        AlignPathArgs ap{};
+        ap.logits = c->alz.as<float>(); ap.ld = ldz; ap.classify_num = hp.classify_num;
+        ap.clips = clips.data(); ap.d_clips = c->alclips.as<AlignClip>(); ap.B = B;
+        ap.bp = c->albp.as<uint16_t>();
+        ap.path = c->alout.as<int32_t>(); ap.logprob = c->alout.as<float>() + NT; ap.score = c->alout.as<float>() + 2 * (size_t)NT;
+        ap.between = c->al_ev[2];
+        launch_align_path(ap, s);
+        HIPCHK(hipEventRecord(c->al_ev[3], s));
+        HIPCHK(hipGetLastError());
+        if ((rc = declined_check("aligner monotone path"))) return rc;
+        HIPCHK(hipMemcpyAsync(mout.data(), c->alout.p, mout.size(), hipMemcpyDeviceToHost, s));
+        c->alz_rows = NT;
+        c->al_timed = true;
+    } else if (NT > 0) {
         if ((rc = upload(c, c->ats, rows)) || (rc = ensure(c, c->atx, (size_t)NT * H * 2)) || (rc = ensure(c, c->aam, (size_t)NT * 8)))
             return rc;
         HIPCHK(hipMemsetAsync(c->aam.p, 0, (size_t)NT * 8, s));
@@ -72,8 +122,22 @@ static int align_classes(qasr_ctx *c, const float *const *pcm, const int *n, con
     HIPCHK(hipEventRecord(c->ev[EV_PREFILL], s));
     HIPCHK(hipEventSynchronize(c->ev[EV_PREFILL]));
     classes.assign(B, {});
-    for (int b = 0, k = 0; b < B; b++)
-        for (int i = 0; i < nrows[b]; i++, k++) classes[b].push_back((int32_t)(0xffffffffu - (uint32_t)(keys[k] & 0xffffffffu)));
+    if (mono) {
+        mono->logprob.assign(B, {});
+        mono->score.assign(B, 0.0f);
+        const int32_t *mp = (const int32_t *)mout.data();
+        const float *ml = (const float *)mout.data() + NT, *ms = (const float *)mout.data() + 2 * (size_t)NT;
+        for (int b = 0, k = 0; b < B; b++) {
+            if (NT > 0 && nrows[b] > 0) mono->score[b] = ms[b];
+            for (int i = 0; i < nrows[b]; i++, k++) {
+                classes[b].push_back(mp[k]);
+                mono->logprob[b].push_back(ml[k]);
+            }
+        }
+    } else {
+        for (int b = 0, k = 0; b < B; b++)
+            for (int i = 0; i < nrows[b]; i++, k++) classes[b].push_back((int32_t)(0xffffffffu - (uint32_t)(keys[k] & 0xffffffffu)));
+    }
     if (t) {
         float a = 0, bb = 0, d = 0, tt = 0;
         HIPCHK(hipEventElapsedTime(&a, c->ev[EV_START], c->ev[EV_MEL]));
@@ -85,11 +149,53 @@ static int align_classes(qasr_ctx *c, const float *const *pcm, const int *n, con
     return 0;
 }
 static int align_classes(qasr_ctx *c, const float *pcm, int n, const std::vector<int32_t> &text_ids, std::vector<int32_t> &classes,
-                         qasr_timings *t) {
+                         qasr_timings *t, AlignMono *mono = nullptr) {
     std::vector<std::vector<int32_t>> cls;
-    const int rc = align_classes(c, &pcm, &n, {text_ids}, cls, t);
+    const int rc = align_classes(c, &pcm, &n, {text_ids}, cls, t, mono);
     if (!rc) classes = cls[0];
     return rc;
+}
+
+// the monotone path of B clips, whatever option align_monotone says
+extern "C" int qasr_align_path(qasr_ctx *c, const float *const *pcm, const int *n, const int32_t *const *text_ids, const int *n_text,
+                               int B, int32_t *classes, float *logprobs, float *score, int cap, int *n_ts, qasr_timings *t) {
+    if (!c || !pcm || !n || !n_text || !n_ts || B <= 0 || cap < 0) return fail(QASR_ERR_ARG, "bad arguments");
+    std::vector<std::vector<int32_t>> ids(B), cls;
+    for (int b = 0; b < B; b++) {
+        if (!pcm[b] || n[b] <= 0 || n_text[b] < 0 || (n_text[b] && (!text_ids || !text_ids[b]))) return fail(QASR_ERR_ARG, "bad arguments");
+        ids[b].assign(text_ids[b], text_ids[b] + n_text[b]);
+    }
+    AlignMono mono;
+    const int rc = align_classes(c, pcm, n, ids, cls, t, &mono);
+    if (rc) return rc;
+    for (int b = 0; b < B; b++) {
+        n_ts[b] = (int)cls[b].size();
+        for (int i = 0; i < n_ts[b] && i < cap; i++) {
+            if (classes) classes[(size_t)b * cap + i] = cls[b][i];
+            if (logprobs) logprobs[(size_t)b * cap + i] = mono.logprob[b][i];
+        }
+        if (score) score[b] = mono.score[b];
+    }
+    return 0;
+}
+
+extern "C" int qasr_align_path_host(const float *logits, int64_t ld, int NT, int classify_num, int C, int32_t *classes,
+                                    float *logprobs, float *score) {
+    if (!align_path_host(logits, ld, NT, classify_num, C, classes, logprobs, score))
+        return fail(QASR_ERR_ARG, "align path: needs NT >= 0, 1 <= C <= classify_num <= ld and the logits");
+    return 0;
+}
+
+extern "C" int qasr_align_path_last_us(qasr_ctx *c, int *us) {
+    if (!c || !us) return fail(QASR_ERR_ARG, "bad arguments");
+    if (!c->al_timed) return fail(QASR_ERR_STATE, "no monotone aligner pass with timestamp rows has run on this context");
+    HIPCHK(hipSetDevice(c->m->device));
+    for (int k = 0; k < 3; k++) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, c->al_ev[k], c->al_ev[k + 1]));
+        us[k] = (int)std::lround(ms * 1000.0f);
+    }
+    return 0;
 }
 
 extern "C" int qasr_align(qasr_ctx *c, const float *pcm, int n, const int32_t *text_ids, int n_text, int32_t *classes,
@@ -170,7 +276,10 @@ static std::string json_escape(const std::string &s) {   // src/main.cpp:230-254
 // whole alignment -> the CLI's JSON document (src/main.cpp:257-276); returns
 // the JSON length (excluding NUL) or minus the error code; writes at most
 // cap-1 bytes + NUL
-static std::string align_doc(const qasr_model *m, const std::vector<std::string> &words, const std::vector<int32_t> &cls, int n);
+// lp (option align_monotone): cls is the monotone path, kept as it is, and every word gains the log-probabilities of
+// its two boundaries
+static std::string align_doc(const qasr_model *m, const std::vector<std::string> &words, const std::vector<int32_t> &cls, int n,
+                             const std::vector<float> *lp = nullptr);
 static int put_str(const std::string &js, char *out, int cap) {
     if (out && cap > 0) {
         const size_t k = std::min(js.size(), (size_t)cap - 1);
@@ -186,9 +295,11 @@ extern "C" int qasr_align_json(qasr_ctx *c, const float *pcm, int n, const char 
     std::vector<std::string> words;
     const std::vector<int32_t> ids = align_tokens(m, text, language ? language : "", words);
     std::vector<int32_t> cls;
-    int rc = align_classes(c, pcm, n, ids, cls, t);
+    AlignMono mono;
+    const bool on = c->fuse.align_monotone != 0;
+    int rc = align_classes(c, pcm, n, ids, cls, t, on ? &mono : nullptr);
     if (rc) return -rc;
-    return put_str(align_doc(m, words, cls, n), out, cap);
+    return put_str(align_doc(m, words, cls, n, on ? &mono.logprob[0] : nullptr), out, cap);
 }
 
 // B clips in one aligner pass (align_classes' batch form): the documents as
@@ -203,25 +314,32 @@ extern "C" int qasr_align_json_batch(qasr_ctx *c, const float *const *pcm, const
         if (!pcm[b] || n[b] <= 0 || !text[b]) return -fail(QASR_ERR_ARG, "bad arguments");
         ids[b] = align_tokens(m, text[b], language ? language : "", words[b]);
     }
-    int rc = align_classes(c, pcm, n, ids, cls, t);
+    AlignMono mono;
+    const bool on = c->fuse.align_monotone != 0;
+    int rc = align_classes(c, pcm, n, ids, cls, t, on ? &mono : nullptr);
     if (rc) return -rc;
     std::string js = "[";
-    for (int b = 0; b < B; b++) js += (b ? ",\n" : "") + align_doc(m, words[b], cls[b], n[b]);
+    for (int b = 0; b < B; b++) js += (b ? ",\n" : "") + align_doc(m, words[b], cls[b], n[b], on ? &mono.logprob[b] : nullptr);
     return put_str(js + "]", out, cap);
 }
 
 // the CLI's document for one clip (src/main.cpp:257-276)
-static std::string align_doc(const qasr_model *m, const std::vector<std::string> &words, const std::vector<int32_t> &cls, int n) {
-    const std::vector<int32_t> fixed = fix_timestamp_classes(cls);
+static std::string align_doc(const qasr_model *m, const std::vector<std::string> &words, const std::vector<int32_t> &cls, int n,
+                             const std::vector<float> *lp) {
+    const std::vector<int32_t> fixed = lp ? cls : fix_timestamp_classes(cls);
     const float dur = (float)n / 16000.0f, seg = m->hp.ts_segment_ms / 1000.0f;
     std::vector<float> ts(fixed.size());
     for (size_t i = 0; i < fixed.size(); i++) ts[i] = std::min(fixed[i] * seg, dur);
     std::string js = "{\n  \"words\": [\n";
     for (size_t i = 0; i < words.size(); i++) {
         const float st = 2 * i < ts.size() ? ts[2 * i] : 0.0f, en = 2 * i + 1 < ts.size() ? ts[2 * i + 1] : dur;
-        char b[64];
+        char b[128];
         js += "    {\"word\": \"" + json_escape(words[i]) + "\", ";
-        snprintf(b, sizeof b, "\"start\": %.3f, \"end\": %.3f}", st, en);
+        if (lp)
+            snprintf(b, sizeof b, "\"start\": %.3f, \"end\": %.3f, \"start_logprob\": %.4f, \"end_logprob\": %.4f}", st, en,
+                     2 * i < lp->size() ? (*lp)[2 * i] : 0.0f, 2 * i + 1 < lp->size() ? (*lp)[2 * i + 1] : 0.0f);
+        else
+            snprintf(b, sizeof b, "\"start\": %.3f, \"end\": %.3f}", st, en);
         js += b;
         if (i + 1 < words.size()) js += ",";
         js += "\n";

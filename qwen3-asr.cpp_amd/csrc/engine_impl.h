@@ -34,6 +34,7 @@
 #include "score_host.h"
 #include "resample_host.h"
 #include "segment_host.h"
+#include "align_path_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -270,6 +271,12 @@ struct qasr_ctx {
     std::vector<long> seg_rec_off;     // per recording: its first sample in c->pcm
     std::vector<double> seg_peak;      // per pool entry
     std::vector<int> seg_silent;
+    // the aligner's monotone path (engine_align.hip): the fp32 logits of every timestamp row
+    // [alz_rows][cls_rows], the backpointer scratch, the clip list, the outputs (path | logprob | score, one copy back)
+    DevBuf alz, albp, alclips, alout;
+    long alz_rows = 0;
+    bool al_timed = false;             // the last monotone pass recorded al_ev (qasr_align_path_last_us)
+    hipEvent_t al_ev[4] = {};          // before the fp32 GEMM, after it, between the two kernels, after the row kernel
     // pinned host staging for small per-call tables (reset at each top-level call)
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
@@ -341,6 +348,7 @@ struct qasr_ctx {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : rs_ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : sg_ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : al_ev) if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
         if (st) (void)hipStreamDestroy(st);
     }

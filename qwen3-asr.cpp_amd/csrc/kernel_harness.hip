@@ -999,3 +999,52 @@ extern "C" int qasr_kt_conv(int device, qasr_kt_conv_args *a) {
     if ((rc = finish(a, true))) return rc;
     return get(out, a->out);
 }
+
+// launch_align_path (csrc/align_path.hip) on B clips whose rows follow each other in the logits.  The logits are
+// followed by `guard` rows of 0xFF bytes; every output has `guard` elements of 0xFF bytes before and after it and
+// comes back whole.  launches == 2: a second launch on the same inputs into the *2 outputs.
+extern "C" int qasr_kt_align_path(int device, qasr_kt_align_path_args *a) {
+    if (!a || a->B <= 0 || a->guard < 1 || a->ld <= 0 || !a->NT || !a->C || !a->path || !a->logprob || !a->lse || !a->score ||
+        a->launches < 1 || a->launches > 2 || (a->launches == 2 && !(a->path2 && a->logprob2 && a->lse2 && a->score2)))
+        return fail(QASR_ERR_ARG, "bad arguments");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int B = a->B, G = a->guard;
+    std::vector<AlignClip> clips(B);
+    long rows = 0;
+    int maxC = 1;
+    for (int b = 0; b < B; b++) {
+        clips[b].NT = a->NT[b];
+        clips[b].C = a->C[b];
+        rows += std::max(a->NT[b], 0);
+        maxC = std::max(maxC, a->C[b]);
+    }
+    if (rows > 0 && !a->logits) return fail(QASR_ERR_ARG, "bad arguments");
+    const long bp_elems = align_path_layout(clips.data(), B);
+    KtBuf in, dclips, bp, path[2], lp[2], lse[2], score[2];
+    if ((rc = put_in(in, rows ? (const void *)a->logits : (const void *)&rows, rows, a->ld, 4, G, 0xFF)) ||
+        (rc = put_state(dclips, clips.data(), clips.size() * sizeof(AlignClip))))
+        return rc;
+    bp.bytes = (size_t)std::max(bp_elems, 8L) * 2;
+    HIPCHK(hipMalloc((void **)&bp.d, bp.bytes));
+    HIPCHK(hipMemset(bp.d, 0xFF, bp.bytes));
+    int32_t *hp[2] = {a->path, a->path2};
+    float *hl[2] = {a->logprob, a->logprob2}, *hs[2] = {a->lse, a->lse2}, *hc[2] = {a->score, a->score2};
+    bool ran = true;
+    for (int l = 0; l < a->launches; l++) {
+        if ((rc = put_out(path[l], hp[l], rows, 1, 4, G)) || (rc = put_out(lp[l], hl[l], rows, 1, 4, G)) ||
+            (rc = put_out(lse[l], hs[l], rows, 1, 4, G)) || (rc = put_out(score[l], hc[l], B, 1, 4, G)))
+            return rc;
+        AlignPathArgs g{};
+        g.logits = in.ptr<float>(); g.ld = a->ld; g.classify_num = a->classify_num;
+        g.clips = clips.data(); g.d_clips = dclips.ptr<AlignClip>(); g.B = B;
+        g.bp = bp.ptr<uint16_t>();
+        g.path = path[l].ptr<int32_t>(); g.logprob = lp[l].ptr<float>(); g.lse = lse[l].ptr<float>(); g.score = score[l].ptr<float>();
+        ran = launch_align_path(g, nullptr) && ran;
+    }
+    a->bt_rows = align_path_bt_rows(std::min(maxC, kAlignPathMaxC));
+    if ((rc = finish(a, ran))) return rc;
+    for (int l = 0; l < a->launches; l++)
+        if ((rc = get(path[l], hp[l])) || (rc = get(lp[l], hl[l])) || (rc = get(lse[l], hs[l])) || (rc = get(score[l], hc[l]))) return rc;
+    return 0;
+}

@@ -57,6 +57,39 @@ void launch_segment(const float *pcm, const SegmentRec *recs, int B, const int2 
                     hipStream_t st, hipEvent_t between = nullptr);
 int segment_tile();
 
+// ---------------------------------------------------------------- forced aligner: the monotone path
+// One entry per clip (csrc/align_path_host.h states the rule): its NT timestamp rows start at row row_off of the
+// logits (clips tile the rows in order: row_off is the sum of the NT before it), its backpointer scratch at element
+// bp_off of bp (NT rows of align_path_bp_ld(C) uint16, bp_off % 8 == 0); C classes are allowed.
+struct AlignClip {
+    long row_off, bp_off;
+    int NT, C;
+};
+constexpr int kAlignPathMaxC = 8192;
+inline constexpr int align_path_bp_ld(int C) { return (C + 15) / 16 * 16; }
+// fills row_off and bp_off of B clips from their NT and C; returns the uint16 elements of scratch they need
+long align_path_layout(AlignClip *clips, int B);
+// backpointer rows of one LDS block of the walk back at C allowed classes
+int align_path_bt_rows(int C);
+struct AlignPathArgs {
+    const float *logits; long ld;       // [rows][ld] fp32, 16-byte aligned, ld % 4 == 0
+    int classify_num;                   // the columns of the log-sum-exp, <= ld
+    const AlignClip *clips;             // host copy (checked here; the largest C picks the template)
+    const AlignClip *d_clips;           // the same on the device
+    int B;
+    uint16_t *bp;                       // scratch, 16-byte aligned
+    int32_t *path; float *logprob;      // [rows]
+    float *lse;                         // [rows], may be null
+    float *score;                       // [B]
+    hipEvent_t between;                 // recorded between the path and the row kernel (may be null)
+};
+// align_path_kernel (one workgroup a clip; 64 x 1, 64 x 8, 256 x 16 or 512 x 16 threads x classes a thread for the
+// largest C <= 64, 512, 4096, 8192) and align_lse_kernel (one workgroup a row).  Returns false, launching and
+// writing nothing, for a clip with C < 1, C > 8192, C > classify_num or NT < 0, classify_num > ld, ld % 4 != 0,
+// offsets that do not tile, or misaligned buffers (note_declined_shape).  Clips with NT = 0 are legal and write
+// nothing.
+bool launch_align_path(const AlignPathArgs &a, hipStream_t st);
+
 // ---------------------------------------------------------------- conv front-end
 // One entry per 100-frame mel chunk (src/audio_encoder.cpp:331-409).
 // conv2 / conv3 weight row length: 9 * channels rounded up to 128, zeros past 9 * channels
@@ -335,6 +368,9 @@ struct FuseCfg {
                                         // LM head (lmh_topk above); 0: nothing changes
     int beam_width = 0;                 // W in 2 .. 8: qasr_run decodes by beam search of width W (engine_beam.hip);
                                         // 0 / 1: greedy, nothing changes
+    int align_monotone = 0;             // aligner models: qasr_align_json* take the monotone path over the classify
+                                        // head's fp32 logits (align_path.hip) and add the log-probabilities of the
+                                        // boundaries; 0: nothing changes
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device

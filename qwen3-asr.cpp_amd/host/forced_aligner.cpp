@@ -136,13 +136,18 @@ alignment_result ForcedAligner::align(const float *samples, int n_samples, const
     std::vector<int32_t> cls(std::max<size_t>(ids.size(), 1));
     int nts = 0;
     qasr_timings tm{};
-    if (qasr_align(ctx_, samples, n_samples, ids.data(), (int)ids.size(), cls.data(), (int)cls.size(), &nts, &tm) != 0) {
+    std::vector<float> lp(cls.size(), 0.0f);
+    const int32_t *idp = ids.data();
+    const int n_ids = (int)ids.size();
+    const int rc = monotone_ ? qasr_align_path(ctx_, &samples, &n_samples, &idp, &n_ids, 1, cls.data(), lp.data(), nullptr, (int)cls.size(), &nts, &tm)
+                             : qasr_align(ctx_, samples, n_samples, ids.data(), n_ids, cls.data(), (int)cls.size(), &nts, &tm);
+    if (rc != 0) {
         result.error_msg = std::string("Decoder forward pass failed: ") + qasr_last_error();
         return result;
     }
     cls.resize(nts);
-    std::vector<int32_t> fixed(nts);
-    if (nts) qasr_fix_timestamps(cls.data(), nts, fixed.data());
+    std::vector<int32_t> fixed(cls);   // (the monotone path needs no repair)
+    if (nts && !monotone_) qasr_fix_timestamps(cls.data(), nts, fixed.data());
     // classes_to_timestamps + clamp (src/forced_aligner.cpp:1267-1278, 1694-1714)
     const float seg = hparams_.timestamp_segment_time_ms / 1000.0f;
     std::vector<float> ts(nts);
@@ -152,6 +157,10 @@ alignment_result ForcedAligner::align(const float *samples, int n_samples, const
         aw.word = words[i];
         aw.start = 2 * i < ts.size() ? ts[2 * i] : 0.0f;
         aw.end = 2 * i + 1 < ts.size() ? ts[2 * i + 1] : audio_duration;
+        if (monotone_) {
+            aw.start_logprob = 2 * i < ts.size() ? lp[2 * i] : 0.0f;
+            aw.end_logprob = 2 * i + 1 < ts.size() ? lp[2 * i + 1] : 0.0f;
+        }
         result.words.push_back(aw);
     }
     result.t_mel_ms = (int64_t)tm.t_mel_ms;

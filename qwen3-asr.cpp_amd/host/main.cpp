@@ -57,6 +57,7 @@ struct cli_params {
     double segment_max_s = 30.0, segment_min_s = 10.0, skip_silence_db = 1.0;   // (skip_silence_db > 0: nothing skipped)
     std::vector<std::string> score_texts;   // --score: texts scored as transcripts of the -f file (Qwen3ASR::score)
     bool align_mode = false, transcribe_align_mode = false;
+    bool align_monotone = false;   // --align-monotone: the aligner's monotone path with log-probabilities (ForcedAligner::set_monotone)
 };
 
 static void usage(const char *prog) {
@@ -110,6 +111,8 @@ static void usage(const char *prog) {
     fprintf(stderr, "\nForced Alignment:\n");
     fprintf(stderr, "  --align                Enable forced alignment mode\n");
     fprintf(stderr, "  --text <text>          Reference transcript for alignment\n");
+    fprintf(stderr, "  --align-monotone       With --align / --transcribe-align: timestamps from the best non-decreasing class path over\n");
+    fprintf(stderr, "                         the model's logits, found on the GPU, and start_logprob / end_logprob for every word\n");
     fprintf(stderr, "\nTranscribe + Align:\n");
     fprintf(stderr, "  -a, --transcribe-align Run ASR then forced alignment\n");
     fprintf(stderr, "  --aligner-model <path> Path to forced aligner GGUF model (required with --transcribe-align)\n");
@@ -272,6 +275,7 @@ static bool parse(int argc, char **argv, cli_params &p) {
         else if (!strcmp(a, "--profile")) p.profile = true;
         else if (!strcmp(a, "--align")) p.align_mode = true;
         else if (!strcmp(a, "-a") || !strcmp(a, "--transcribe-align")) p.transcribe_align_mode = true;
+        else if (!strcmp(a, "--align-monotone")) p.align_monotone = true;
         else if (!strcmp(a, "--aligner-model")) { if (!val(p.aligner_model_path)) return false; }
         else if (!strcmp(a, "--text")) { if (!val(p.align_text)) return false; }
         else if (!strcmp(a, "-h") || !strcmp(a, "--help")) { usage(argv[0]); exit(0); }
@@ -288,6 +292,10 @@ static bool parse(int argc, char **argv, cli_params &p) {
         return false;
     }
     // src/main.cpp:76-90
+    if (p.align_monotone && !p.align_mode && !p.transcribe_align_mode) {
+        fprintf(stderr, "Error: --align-monotone needs --align or --transcribe-align\n");
+        return false;
+    }
     if (p.align_mode && p.align_text.empty()) {
         fprintf(stderr, "Error: Reference text is required for alignment mode (--text)\n");
         return false;
@@ -357,12 +365,16 @@ static std::string escape_json_string(const std::string &s) {
     return r;
 }
 
-static std::string alignment_to_json(const qwen3_asr::alignment_result &result) {
+static std::string alignment_to_json(const qwen3_asr::alignment_result &result, bool logprobs = false) {
     std::string json = "{\n  \"words\": [\n";
     for (size_t i = 0; i < result.words.size(); ++i) {
         const auto &w = result.words[i];
-        char buf[64];
-        snprintf(buf, sizeof buf, "\"start\": %.3f, \"end\": %.3f}", w.start, w.end);
+        char buf[128];
+        if (logprobs)
+            snprintf(buf, sizeof buf, "\"start\": %.3f, \"end\": %.3f, \"start_logprob\": %.4f, \"end_logprob\": %.4f}", w.start, w.end,
+                     w.start_logprob, w.end_logprob);
+        else
+            snprintf(buf, sizeof buf, "\"start\": %.3f, \"end\": %.3f}", w.start, w.end);
         json += "    {\"word\": \"" + escape_json_string(w.word) + "\", " + buf;
         if (i + 1 < result.words.size()) json += ",";
         json += "\n";
@@ -416,6 +428,7 @@ static int run_alignment(const cli_params &p) {
     qwen3_asr::ForcedAligner al;
     if (!load_aligner(al, p.model_path, p.language, p.device)) return 1;
     al.set_resample(p.resample);
+    al.set_monotone(p.align_monotone);
     fprintf(stderr, "Model loaded. Running alignment...\n");
     auto r = al.align(p.audio_paths[0], p.align_text, p.language);
     if (!r.success) { fprintf(stderr, "Error: %s\n", r.error_msg.c_str()); return 1; }
@@ -427,7 +440,7 @@ static int run_alignment(const cli_params &p) {
         fprintf(stderr, "  Total:           %lld ms\n", (long long)r.t_total_ms);
         fprintf(stderr, "  Words aligned:   %zu\n", r.words.size());
     }
-    return write_output(p, alignment_to_json(r) + "\n");
+    return write_output(p, alignment_to_json(r, p.align_monotone) + "\n");
 }
 
 static int run_transcribe_and_align(const cli_params &p) {
@@ -457,6 +470,7 @@ static int run_transcribe_and_align(const cli_params &p) {
     qwen3_asr::ForcedAligner al;
     if (!load_aligner(al, p.aligner_model_path, lang, p.device)) return 1;
     al.set_resample(p.resample);
+    al.set_monotone(p.align_monotone);
     auto r = al.align(p.audio_paths[0], transcript, lang);
     if (!r.success) { fprintf(stderr, "Error (Aligner): %s\n", r.error_msg.c_str()); return 1; }
     if (p.print_timing) {
@@ -466,7 +480,7 @@ static int run_transcribe_and_align(const cli_params &p) {
         fprintf(stderr, "  Total:         %lld ms\n", (long long)(ar.t_total_ms + r.t_total_ms));
         fprintf(stderr, "  Words aligned: %zu\n", r.words.size());
     }
-    return write_output(p, alignment_to_json(r) + "\n");
+    return write_output(p, alignment_to_json(r, p.align_monotone) + "\n");
 }
 
 // the sample rate a WAV file's header states (fmt chunk first, as write_wav and most encoders lay it out); 16000

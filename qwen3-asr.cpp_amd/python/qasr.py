@@ -44,6 +44,7 @@ EXPORTS = [
     "qasr_resample_plan", "qasr_resample_len", "qasr_resample_taps", "qasr_resample_host",
     "qasr_resample", "qasr_resample_last_us", "qasr_stage_audio_rate", "qasr_transcribe_batch_rate", "qasr_run_stream_rate",
     "qasr_segment_validate", "qasr_segment_host", "qasr_segment", "qasr_segment_last_us", "qasr_stage_long", "qasr_get_segments",
+    "qasr_align_path", "qasr_align_path_host", "qasr_align_path_last_us",
 ]
 
 
@@ -184,6 +185,9 @@ def lib() -> C.CDLL:
             "qasr_segment_last_us": ([P, IP], I),
             "qasr_stage_long": ([P, C.POINTER(F), IP, IP, I, C.POINTER(SegmentParams)], I),
             "qasr_get_segments": ([P, I, C.POINTER(C.c_longlong), IP, DP, IP, I], I),
+            "qasr_align_path": ([P, C.POINTER(F), IP, C.POINTER(I32P), IP, I, I32P, F, F, I, IP, C.POINTER(Timings)], I),
+            "qasr_align_path_host": ([F, C.c_int64, I, I, I, I32P, F, F], I),
+            "qasr_align_path_last_us": ([P, IP], I),
             "qasr_set_token_callback": ([P, TOKEN_CB, P], I),
             "qasr_set_profile": ([P, I], I), "qasr_profile_report": ([P, C.c_char_p, I], I),
             "qasr_detokenize": ([P, I32P, I, C.c_char_p, I], I), "qasr_tokenize": ([P, C.c_char_p, I32P, I], I),
@@ -386,6 +390,17 @@ def segment_host(pcm: np.ndarray, **kw) -> List["Segment"]:
     _neg(lib().qasr_segment_host(_f(pcm), len(pcm), C.byref(p), _i(cuts), _d(peak), _i(silent), K), "qasr_segment_host")
     ends = [int(c) * 160 for c in cuts[1:]] + [len(pcm)]
     return [Segment(0, int(cuts[k]) * 160, ends[k] - int(cuts[k]) * 160, float(peak[k]), bool(silent[k])) for k in range(K)]
+
+
+def align_path_host(logits: np.ndarray, C_allowed: int, classify_num: Optional[int] = None):
+    """the monotone path's rule on the CPU (qasr_align_path_host): logits [NT][ld] fp32, C_allowed
+    classes allowed, the log-sum-exp over classify_num columns (default: all) -> (classes, logprobs, score)"""
+    z = np.ascontiguousarray(logits, np.float32)
+    NT, ld = z.shape
+    N = ld if classify_num is None else int(classify_num)
+    cls, lp, sc = np.zeros(max(NT, 1), np.int32), np.zeros(max(NT, 1), np.float32), np.zeros(1, np.float32)
+    _check(lib().qasr_align_path_host(_f(z) if NT else None, ld, NT, N, int(C_allowed), _i32(cls), _f(lp), _f(sc)), "qasr_align_path_host")
+    return cls[:NT].copy(), lp[:NT].copy(), float(sc[0])
 
 
 def fix_timestamps(classes: Sequence[int]) -> List[int]:
@@ -1099,9 +1114,58 @@ class Context:
                                 C.byref(nts), C.byref(t)), "qasr_align")
         return out[:nts.value].tolist(), t
 
-    def align_json(self, pcm: np.ndarray, text: str, language: str = ""):
+    def align_path(self, pcms, text_ids):
+        """qasr_align_path: the monotone path of B clips in one aligner pass -> per clip
+        (classes, logprobs, score): non-decreasing classes, the log-probability of each, the path's summed logit"""
+        arrs = [np.ascontiguousarray(p, np.float32) for p in pcms]
+        ids = [np.ascontiguousarray(t, np.int32) for t in text_ids]
+        B = len(arrs)
+        n = np.array([len(a) for a in arrs], np.int32)
+        nt = np.array([len(t) for t in ids], np.int32)
+        cap = max(1, max(int(np.sum(t == self.model.hp.timestamp_token_id)) for t in ids))
+        ptrs = (C.POINTER(C.c_float) * B)(*[_f(a) for a in arrs])
+        tptrs = (C.POINTER(C.c_int32) * B)(*[_i32(t) if len(t) else _i32(np.zeros(1, np.int32)) for t in ids])
+        cls, lp = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.float32)
+        sc, nts = np.zeros(B, np.float32), np.zeros(B, np.int32)
+        t = Timings()
+        _check(lib().qasr_align_path(self.h, ptrs, _i(n), tptrs, _i(nt), B, _i32(cls), _f(lp), _f(sc), cap, _i(nts), C.byref(t)),
+               "qasr_align_path")
+        self.last_align_timings = t
+        return [(cls[b, :nts[b]].tolist(), lp[b, :nts[b]].copy(), float(sc[b])) for b in range(B)]
+
+    def align_logits(self, rows: int) -> np.ndarray:
+        """qasr_debug_read "align_logits": the fp32 classify-head logits of the last monotone pass's first `rows`
+        timestamp rows (the clips' rows in order), [rows][classify_num rounded up to 64]"""
+        out = np.zeros((rows, (self.model.hp.classify_num + 63) // 64 * 64), np.float32)
+        _check(lib().qasr_debug_read(self.h, b"align_logits", out.ctypes.data_as(C.c_void_p), out.nbytes), "qasr_debug_read")
+        return out
+
+    def align_path_last_us(self) -> Tuple[int, int, int]:
+        """device time of the last monotone pass's fp32 classify GEMM, path kernel and row kernel, microseconds"""
+        us = np.zeros(3, np.int32)
+        _check(lib().qasr_align_path_last_us(self.h, _i(us)), "qasr_align_path_last_us")
+        return int(us[0]), int(us[1]), int(us[2])
+
+    def _monotone(self, monotone):
+        """option align_monotone set for one call: -> the value to restore, or None"""
+        if monotone is None or int(bool(monotone)) == self.get_option("align_monotone"):
+            return None
+        old = self.get_option("align_monotone")
+        self.set_option("align_monotone", int(bool(monotone)))
+        return old
+
+    def align_json(self, pcm: np.ndarray, text: str, language: str = "", monotone: Optional[bool] = None):
         """ForcedAligner::align -> the CLI JSON document (parsed) and timings.
-        qasr_align_json returns the document length, or minus an error code."""
+        qasr_align_json returns the document length, or minus an error code.
+        monotone: option align_monotone for this call (None: as the context has it)"""
+        old = self._monotone(monotone)
+        try:
+            return self._align_json(pcm, text, language)
+        finally:
+            if old is not None:
+                self.set_option("align_monotone", old)
+
+    def _align_json(self, pcm, text, language):
         import json
         pcm = np.ascontiguousarray(pcm, np.float32)
         t = Timings()
@@ -1115,9 +1179,17 @@ class Context:
             lib().qasr_align_json(self.h, _f(pcm), len(pcm), text.encode(), language.encode(), buf, n + 1, C.byref(t))
         return json.loads(buf.raw[:n].decode("utf-8")), t
 
-    def align_json_batch(self, pcms, texts, language: str = ""):
+    def align_json_batch(self, pcms, texts, language: str = "", monotone: Optional[bool] = None):
         """qasr_align_json_batch: B clips in one aligner pass -> (list of the
-        CLI documents, parsed, in input order; timings)"""
+        CLI documents, parsed, in input order; timings).  monotone: as align_json's"""
+        old = self._monotone(monotone)
+        try:
+            return self._align_json_batch(pcms, texts, language)
+        finally:
+            if old is not None:
+                self.set_option("align_monotone", old)
+
+    def _align_json_batch(self, pcms, texts, language):
         import json
         arrs = [np.ascontiguousarray(p, np.float32) for p in pcms]
         B = len(arrs)
