@@ -1198,6 +1198,86 @@ typedef struct {
 } qasr_kt_align_path_args;
 int qasr_kt_align_path(int device, qasr_kt_align_path_args *a);
 
+/* test only: launch_lmhead_batch (csrc/lmhead.hip) on caller-given arrays (tests/lmhead_util.py holds the bindings).
+ * Inputs x [M][ldx], norm_w [K] and W [N][K] are followed by `guard` rows of 0xFF bytes (norm_w: one).  Pure outputs
+ * (out_f32, tok_out, lp_out, tk_out, tk_lp: optional but tok_out) are [M + 2 guard] rows, every byte 0xFF before the
+ * launch, and come back whole.  In / out arrays (hist, lp_hist, tk_hist, tk_lphist, pos, nkv) are passed as their
+ * whole allocations, [M + 2 guard] rows with the guard rows as the caller filled them, uploaded and returned whole;
+ * step [1] likewise.  amax [128 + 2 guard] and done [1] are zero before the first launch and come back as the last
+ * launch left them.  The (m, s) and top-K partials of lmhead_grid() workgroups are the entry's own, every byte 0xFF
+ * before the first launch.  launches: back-to-back launches on the same arrays, no host reset between them
+ * (step + launches < hist_stride).  A shape or pointer group the launcher does not take is `declined`; the entry
+ * itself refuses (QASR_ERR_ARG) only what would make a taken launch read or write outside these arrays. */
+typedef struct {
+    int32_t M, N, K;
+    int32_t ldx, ldo, hist_stride;
+    int32_t n_valid, keep_step, tk_k;
+    int32_t guard, launches;
+    float eps;
+    const float *x;          /* fp32 [M][ldx] */
+    const float *norm_w;     /* [K] */
+    const uint16_t *W;       /* fp16 [N][K] */
+    float *out_f32;          /* [M + 2 guard][ldo] or null */
+    int32_t *tok_out;        /* [M + 2 guard] */
+    int32_t *hist;           /* [M + 2 guard][hist_stride] in / out, or null */
+    int32_t *pos;            /* [M + 2 guard] in / out */
+    int32_t *nkv;            /* [M + 2 guard] in / out, or null */
+    int32_t *step;           /* [1] in / out */
+    /* the lp_* group: lp_part is the entry's own, wanted when use_lp_part is set */
+    int32_t use_lp_part;
+    float *lp_out;           /* [M + 2 guard] */
+    float *lp_hist;          /* [M + 2 guard][hist_stride] in / out */
+    /* the tk_* group: tk_part is the entry's own, wanted when use_tk_part is set */
+    int32_t use_tk_part;
+    int32_t *tk_out;         /* [M + 2 guard][tk_k] */
+    float *tk_lp;            /* [M + 2 guard][tk_k] */
+    int32_t *tk_hist;        /* [M + 2 guard][hist_stride * tk_k] in / out */
+    float *tk_lphist;        /* [M + 2 guard][hist_stride * tk_k] in / out */
+    uint64_t *amax;          /* [128 + 2 guard] out */
+    uint32_t *done;          /* [1] out */
+    int32_t grid;            /* out: lmhead_grid() */
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_lmhead_args;
+int qasr_kt_lmhead(int device, qasr_kt_lmhead_args *a);
+/* lmhead_grid() of the device alone (the tests size their vocabularies by it) */
+int qasr_kt_lmhead_grid(int device, int32_t *grid);
+
+/* test only: the row kernels of csrc/elementwise.hip behind the LM head, one launcher a call.  Inputs are followed by
+ * `guard` rows of 0xFF bytes, outputs are [rows + 2 guard] rows of 0xFF bytes before the launch and come back whole;
+ * in / out arrays are passed, uploaded and returned as whole allocations with the caller's guard rows.  Indices are
+ * checked against their arrays before any launch (QASR_ERR_ARG).  tag is set by the two launchers that record one.
+ *   op 0 launch_token_logprob  f_in logits [in_rows][ld], i_in tok [B] (row b reads logits row b / src_div),
+ *                              f_out lp_out [B], f_hist lp_hist [B][hist_stride] in / out or null (slot `step`)
+ *   op 1 launch_topk_rows      f_in logits [B][ld], f_out tk_lp [B][K], i_out tk_ids [B][K], f_hist / i_hist the
+ *                              histories [B][hist_stride * K] in / out, both or none
+ *   op 2 launch_argmax_finish  u_in keys [B], i_out ids [B], i_hist hist [B][hist_stride] in / out or null; B <= 256
+ *   op 3 launch_embed          i_in ids [B], h_in embd fp16 [in_rows][ld], f_in audio [in_rows2][ld] and i_in2
+ *                              row_audio [B] (both or none), f_out x [B][ld]
+ *   op 4 launch_gather_rows    f_in src [in_rows][ld], i_in idx [B], f_out dst [B][ld]; ld % 4 == 0
+ *   op 5 launch_step_advance   i_out pos [B] in / out, i_hist nkv [B] in / out, step in / out; B <= 256
+ *   op 6 launch_fill_u64       u_out [B] <- fill */
+typedef struct {
+    int32_t op;
+    int32_t B, ld, in_rows, in_rows2;
+    int32_t n_valid, K, src_div, hist_stride, step;
+    int32_t guard;
+    uint64_t fill;
+    const float *f_in;
+    const uint16_t *h_in;
+    const int32_t *i_in, *i_in2;
+    const uint64_t *u_in;
+    float *f_out, *f_hist;
+    int32_t *i_out, *i_hist;
+    uint64_t *u_out;
+    int32_t step_out;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_rows_args;
+int qasr_kt_rows(int device, qasr_kt_rows_args *a);
+
 #ifdef __cplusplus
 }
 #endif

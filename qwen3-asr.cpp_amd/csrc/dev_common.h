@@ -123,8 +123,17 @@ __device__ __forceinline__ float argmax_key_val(unsigned long long k) {
 // (tests/test_gpu_logprobs*.py, bar 2e-5); the OCML expf cost the one-launch
 // LM head 4x the VALU work per logit.
 __device__ __forceinline__ float lse_exp(float x) { return __expf(x); }
+// -inf values (constrain.hip writes them into logit rows: banned n-grams, suppress, a -inf bias):
+//   lse_add    a -inf value contributes nothing, whatever m is: (m, s) keeps its bits, the empty pair
+//              stays (-inf, 0).  (v - m is NaN when both are -inf: that term is 0 by definition, not
+//              exp(NaN).)  A finite v against m = -inf gives (v, 1).  Finite inputs: the bits they
+//              always had.
+//   lse_merge  a pair with m = -inf has s = 0 by the above (empty, or nothing but -inf values); it
+//              merges as the identity from either side, and two such pairs give (-inf, 0): the m == mn
+//              test keeps exp(-inf - -inf) from being formed.
+//   lse_logprob of a -inf logit is -inf (never NaN) as long as one value of the row is finite.
 __device__ __forceinline__ void lse_add(float &m, float &s, float v) {
-    const float e = lse_exp(-fabsf(v - m));   // (m = -inf: e = 0)
+    const float e = v == -INFINITY ? 0.0f : lse_exp(-fabsf(v - m));   // (m = -inf, v finite: e = 0)
     s = v > m ? s * e + 1.0f : s + e;
     m = fmaxf(m, v);
 }

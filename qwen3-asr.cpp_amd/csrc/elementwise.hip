@@ -296,6 +296,7 @@ void launch_token_logprob(const float *logits, int ld, int B, int n_valid, const
     else
         hipLaunchKernelGGL(token_logprob_kernel<false>, dim3(B), dim3(1024), 0, s, logits, ld, nv, tok, step, lp_out, lp_hist,
                            hist_stride, 1);
+    note_kernel("token_logprob", 2, src_div > 1 ? 1 : 0, (ld & 3) ? 0 : 1);   // <row map, float4 path>
 }
 
 // ------------------------------------------------------- top-K alternatives
@@ -446,6 +447,7 @@ bool launch_topk_rows(const float *logits, int ld, int B, int n_valid, int K, co
     if (B <= 0) return true;
     hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(1024), 0, s, logits, ld, nv, K, step, tk_ids, tk_lp, tk_hist_ids, tk_hist_lp,
                        hist_stride);
+    note_kernel("topk_rows", 2, K, (ld & 3) ? 0 : 1);   // <K, float4 path>
     return true;
 }
 

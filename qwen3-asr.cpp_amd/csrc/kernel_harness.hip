@@ -1048,3 +1048,180 @@ extern "C" int qasr_kt_align_path(int device, qasr_kt_align_path_args *a) {
         if ((rc = get(path[l], hp[l])) || (rc = get(lp[l], hl[l])) || (rc = get(lse[l], hs[l])) || (rc = get(score[l], hc[l]))) return rc;
     return 0;
 }
+
+// ------------------------------------------------- LM heads and the row kernels behind them
+// (tests/test_gpu_lmhead_kernels.py)
+namespace {
+// in / out: the caller's whole allocation, guard + rows + guard rows of ld elements, up and back as it is
+int put_whole(KtBuf &b, const void *host, long rows, long ld, int esz, int guard) {
+    if (!host) return 0;
+    b.bytes = (size_t)(rows + 2 * guard) * ld * esz;
+    b.off = (size_t)guard * ld * esz;
+    HIPCHK(hipMalloc((void **)&b.d, std::max<size_t>(b.bytes, 8)));
+    if (b.bytes) HIPCHK(hipMemcpy(b.d, host, b.bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+// the entry's own scratch, every byte `fill`
+int put_scratch(KtBuf &b, size_t bytes, int fill) {
+    b.bytes = bytes;
+    HIPCHK(hipMalloc((void **)&b.d, bytes));
+    HIPCHK(hipMemset(b.d, fill, bytes));
+    return 0;
+}
+}  // namespace
+
+extern "C" int qasr_kt_lmhead_grid(int device, int32_t *grid) {
+    if (!grid) return fail(QASR_ERR_ARG, "bad arguments");
+    const int rc = use_device(device);
+    if (rc) return rc;
+    *grid = lmhead_grid();
+    return 0;
+}
+
+extern "C" int qasr_kt_lmhead(int device, qasr_kt_lmhead_args *a) {
+    if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || a->tk_k < 0 || !a->x || !a->norm_w || !a->W ||
+        !a->tok_out || !a->pos || !a->step || !a->amax || !a->done)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    // what a taken launch addresses: K floats of every x row, N columns of out_f32, history slot step + 1 of every launch
+    if (a->ldx < a->K || (a->out_f32 && a->ldo < a->N)) return fail(QASR_ERR_ARG, "leading dimensions smaller than the rows");
+    const bool hists = a->hist || a->lp_hist || a->tk_hist || a->tk_lphist;
+    if (hists && (a->hist_stride < 1 || *a->step < 0 || (long)*a->step + a->launches >= a->hist_stride))
+        return fail(QASR_ERR_ARG, "step + launches outside the histories");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int M = a->M, N = a->N, K = a->K, G = a->guard, HS = std::max(a->hist_stride, 1), TK = std::max(a->tk_k, 1);
+    const int grid = lmhead_grid();
+    a->grid = grid;
+    KtBuf x, nw, W, o32, tok, hist, pos, nkv, step, lpp, lpo, lph, tkp, tko, tkl, tkh, tklh, amax, done;
+    if ((rc = put_in(x, a->x, M, a->ldx, 4, G, 0xFF)) || (rc = put_in(nw, a->norm_w, 1, K, 4, 1, 0xFF)) ||
+        (rc = put_in(W, a->W, N, K, 2, G, 0xFF)) || (rc = put_out(o32, a->out_f32, M, a->ldo, 4, G)) ||
+        (rc = put_out(tok, a->tok_out, M, 1, 4, G)) || (rc = put_whole(hist, a->hist, M, HS, 4, G)) ||
+        (rc = put_whole(pos, a->pos, M, 1, 4, G)) || (rc = put_whole(nkv, a->nkv, M, 1, 4, G)) || (rc = put_state(step, a->step, 4)) ||
+        (rc = put_out(lpo, a->lp_out, M, 1, 4, G)) || (rc = put_whole(lph, a->lp_hist, M, HS, 4, G)) ||
+        (rc = put_out(tko, a->tk_out, M, TK, 4, G)) || (rc = put_out(tkl, a->tk_lp, M, TK, 4, G)) ||
+        (rc = put_whole(tkh, a->tk_hist, M, (long)HS * TK, 4, G)) || (rc = put_whole(tklh, a->tk_lphist, M, (long)HS * TK, 4, G)) ||
+        (rc = put_out(amax, a->amax, 128, 1, 8, G)) || (rc = put_scratch(done, 4, 0)))
+        return rc;
+    HIPCHK(hipMemset(amax.ptr<char>(), 0, 128 * 8));
+    if (a->use_lp_part && (rc = put_scratch(lpp, (size_t)grid * 128 * 8, 0xFF))) return rc;
+    if (a->use_tk_part && (rc = put_scratch(tkp, (size_t)grid * 128 * TOPK_MAX * 8, 0xFF))) return rc;
+
+    GemvArgs g{};
+    g.x = x.ptr<float>(); g.ldx = a->ldx;
+    g.norm_w = nw.ptr<float>(); g.eps = a->eps;
+    g.W = W.ptr<uint16_t>();
+    g.K = K; g.N = N; g.M = M;
+    g.out_f32 = o32.ptr<float>(); g.ldo = a->ldo;
+    g.amax = amax.ptr<unsigned long long>();
+    g.done = done.ptr<unsigned int>(); g.tok_out = tok.ptr<int32_t>(); g.hist = hist.ptr<int32_t>();
+    g.hist_stride = a->hist_stride; g.step = step.ptr<int>(); g.pos = pos.ptr<int>(); g.nkv = nkv.ptr<int>();
+    g.n_valid = a->n_valid; g.keep_step = a->keep_step;
+    g.lp_part = lpp.ptr<unsigned long long>(); g.lp_out = lpo.ptr<float>(); g.lp_hist = lph.ptr<float>();
+    g.tk_part = tkp.ptr<unsigned long long>(); g.tk_out = tko.ptr<int32_t>(); g.tk_lp = tkl.ptr<float>();
+    g.tk_hist = tkh.ptr<int32_t>(); g.tk_lphist = tklh.ptr<float>(); g.tk_k = a->tk_k;
+
+    bool ran = true;
+    for (int i = 0; i < a->launches && ran; i++) ran = launch_lmhead_batch(g, nullptr);   // (back to back: no host reset between them)
+    if ((rc = finish(a, ran))) return rc;
+    if ((rc = get(o32, a->out_f32)) || (rc = get(tok, a->tok_out)) || (rc = get(hist, a->hist)) || (rc = get(pos, a->pos)) ||
+        (rc = get(nkv, a->nkv)) || (rc = get(step, a->step)) || (rc = get(lpo, a->lp_out)) || (rc = get(lph, a->lp_hist)) ||
+        (rc = get(tko, a->tk_out)) || (rc = get(tkl, a->tk_lp)) || (rc = get(tkh, a->tk_hist)) || (rc = get(tklh, a->tk_lphist)) ||
+        (rc = get(amax, a->amax)) || (rc = get(done, a->done)))
+        return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_rows(int device, qasr_kt_rows_args *a) {
+    if (!a || a->op < 0 || a->op > 6 || a->B <= 0 || a->guard < 0) return fail(QASR_ERR_ARG, "bad arguments");
+    const int op = a->op, B = a->B, ld = a->ld, G = a->guard, HS = std::max(a->hist_stride, 1);
+    const bool hist_op = op <= 2;
+    if (hist_op && (a->f_hist || a->i_hist) && (a->hist_stride < 1 || a->step < 0 || a->step >= a->hist_stride))
+        return fail(QASR_ERR_ARG, "step outside the history");
+    // every index against its array, before any launch
+    auto inside = [](const int32_t *v, int n, long lim) {
+        for (int i = 0; i < n; i++)
+            if (v[i] < 0 || v[i] >= lim) return false;
+        return true;
+    };
+    bool ok = true;
+    switch (op) {
+        case 0:
+            ok = a->f_in && a->i_in && a->f_out && ld > 0 && a->src_div >= 1 && a->in_rows >= (B + a->src_div - 1) / a->src_div &&
+                 a->n_valid >= 0 && inside(a->i_in, B, ld);
+            break;
+        case 1: ok = a->f_in && ld > 0 && a->in_rows >= B && a->n_valid >= 0 && a->K >= 0 && a->K <= 64; break;   // (K: the launcher's to judge)
+        case 2: ok = a->u_in && a->i_out && B <= 256; break;
+        case 3:
+            ok = a->i_in && a->h_in && a->f_out && ld > 0 && !a->f_in == !a->i_in2;
+            for (int i = 0; ok && i < B; i++) {
+                const bool audio = a->i_in2 && a->i_in2[i] >= 0;
+                ok = audio ? a->i_in2[i] < a->in_rows2 : (a->i_in[i] >= 0 && a->i_in[i] < a->in_rows);
+            }
+            break;
+        case 4: ok = a->f_in && a->i_in && a->f_out && ld > 0 && ld % 4 == 0 && inside(a->i_in, B, a->in_rows); break;
+        case 5: ok = a->i_out && a->i_hist && B <= 256; break;
+        default: ok = a->u_out != nullptr; break;
+    }
+    if (!ok) return fail(QASR_ERR_ARG, "operands missing, or an index outside its array");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int TK = std::max(a->K, 1);
+    KtBuf fin, hin, iin, iin2, uin, fout, fhist, iout, ihist, uout, step;
+    if ((rc = put_state(step, &a->step, 4))) return rc;
+    bool ran = true;
+    switch (op) {
+        case 0:
+            if ((rc = put_in(fin, a->f_in, a->in_rows, ld, 4, G, 0xFF)) || (rc = put_in(iin, a->i_in, 1, B, 4, 0, 0)) ||
+                (rc = put_out(fout, a->f_out, B, 1, 4, G)) || (rc = put_whole(fhist, a->f_hist, B, HS, 4, G)))
+                return rc;
+            launch_token_logprob(fin.ptr<float>(), ld, B, a->n_valid, iin.ptr<int32_t>(), step.ptr<int>(), fout.ptr<float>(),
+                                 fhist.ptr<float>(), a->hist_stride, nullptr, a->src_div);
+            break;
+        case 1:
+            if ((rc = put_in(fin, a->f_in, a->in_rows, ld, 4, G, 0xFF)) || (rc = put_out(fout, a->f_out, B, TK, 4, G)) ||
+                (rc = put_out(iout, a->i_out, B, TK, 4, G)) || (rc = put_whole(fhist, a->f_hist, B, (long)HS * TK, 4, G)) ||
+                (rc = put_whole(ihist, a->i_hist, B, (long)HS * TK, 4, G)))
+                return rc;
+            ran = launch_topk_rows(fin.ptr<float>(), ld, B, a->n_valid, a->K, step.ptr<int>(), iout.ptr<int32_t>(), fout.ptr<float>(),
+                                   ihist.ptr<int32_t>(), fhist.ptr<float>(), a->hist_stride, nullptr);
+            break;
+        case 2:
+            if ((rc = put_in(uin, a->u_in, 1, B, 8, 0, 0)) || (rc = put_out(iout, a->i_out, B, 1, 4, G)) ||
+                (rc = put_whole(ihist, a->i_hist, B, HS, 4, G)))
+                return rc;
+            launch_argmax_finish(uin.ptr<unsigned long long>(), B, iout.ptr<int32_t>(), ihist.ptr<int32_t>(), a->hist_stride, step.ptr<int>(),
+                                 nullptr);
+            break;
+        case 3:
+            if ((rc = put_in(iin, a->i_in, 1, B, 4, 0, 0)) || (rc = put_in(hin, a->h_in, a->in_rows, ld, 2, G, 0xFF)) ||
+                (rc = put_in(fin, a->f_in, a->in_rows2, ld, 4, G, 0xFF)) || (rc = put_in(iin2, a->i_in2, 1, B, 4, 0, 0)) ||
+                (rc = put_out(fout, a->f_out, B, ld, 4, G)))
+                return rc;
+            launch_embed(iin.ptr<int32_t>(), B, hin.ptr<uint16_t>(), ld, fin.ptr<float>(), iin2.ptr<int>(), fout.ptr<float>(), nullptr);
+            break;
+        case 4:
+            if ((rc = put_in(fin, a->f_in, a->in_rows, ld, 4, G, 0xFF)) || (rc = put_in(iin, a->i_in, 1, B, 4, 0, 0)) ||
+                (rc = put_out(fout, a->f_out, B, ld, 4, G)))
+                return rc;
+            launch_gather_rows(fin.ptr<float>(), iin.ptr<int>(), B, ld, fout.ptr<float>(), nullptr);
+            break;
+        case 5:
+            if ((rc = put_whole(iout, a->i_out, B, 1, 4, G)) || (rc = put_whole(ihist, a->i_hist, B, 1, 4, G))) return rc;
+            launch_step_advance(iout.ptr<int>(), ihist.ptr<int>(), step.ptr<int>(), B, nullptr);
+            break;
+        default:
+            if ((rc = put_out(uout, a->u_out, B, 1, 8, G))) return rc;
+            launch_fill_u64(uout.ptr<unsigned long long>(), B, a->fill, nullptr);
+            break;
+    }
+    if (op <= 1) {
+        if ((rc = finish(a, ran))) return rc;
+    } else {
+        if ((rc = finish_plain(&a->declined, true))) return rc;
+        a->tag[0] = a->msg[0] = 0;
+    }
+    if ((rc = get(step, &a->step_out)) || (rc = get(fout, a->f_out)) || (rc = get(fhist, a->f_hist)) || (rc = get(iout, a->i_out)) ||
+        (rc = get(ihist, a->i_hist)) || (rc = get(uout, a->u_out)))
+        return rc;
+    return 0;
+}

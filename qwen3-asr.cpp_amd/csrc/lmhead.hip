@@ -196,6 +196,8 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
     //      together (one row at a time left the weight ring idle for ~10 us at 64 rows)
     constexpr int R = MT * 16 / WPG, RB = R < 4 ? R : 4;
     static_assert(R * WPG == MT * 16, "rows split evenly over the waves");
+    // (the batches need not: MT = 3 has R = 6, a batch of four and one of two -- r0 + r >= R, known at
+    // compile time in the unrolled loops, is a row past the LDS rows and is skipped)
     float4 wv[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) wv[i] = *(const float4 *)(g.norm_w + 4 * lane + 256 * i);
@@ -204,6 +206,7 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
         float4 v[RB][4];
 #pragma unroll
         for (int r = 0; r < RB; r++) {
+            if (r0 + r >= R) continue;
             const int m = wid + WPG * (r0 + r);
             const float *xr = g.x + (long)(m < M ? m : 0) * g.ldx;
 #pragma unroll
@@ -211,6 +214,7 @@ __global__ __launch_bounds__(64 * WPG) void lmhead_batch_kernel(GemvArgs g) {
         }
 #pragma unroll
         for (int r = 0; r < RB; r++) {
+            if (r0 + r >= R) continue;
             const int m = wid + WPG * (r0 + r);
             double s = 0.0;
 #pragma unroll
@@ -386,6 +390,7 @@ void run_lmhead_v(const GemvArgs &g, hipStream_t s) {
         ncu = n > 0 ? n : 256;
     }
     hipLaunchKernelGGL((lmhead_batch_kernel<MT, WPG, D, LSE, TK>), dim3(ncu), dim3(64 * WPG), MT * 16 * LMH_K * 2, s, g);
+    note_kernel("lmhead", 3, MT, LSE ? 1 : 0, TK ? 1 : 0);
 }
 template <int MT>
 void run_lmhead(const GemvArgs &g, hipStream_t s) {
@@ -589,6 +594,7 @@ void run_lmhead128(const GemvArgs &g, hipStream_t s) {
         ncu = n > 0 ? n : 256;
     }
     hipLaunchKernelGGL(lmhead128_kernel<LSE>, dim3(ncu), dim3(512), L128_LDS, s, g);
+    note_kernel("lmhead128", 1, LSE ? 1 : 0);
 }
 
 }  // namespace

@@ -156,6 +156,28 @@ def test_logprobs_and_topk_are_the_edited_rows(tiny):
         c.set_option("top_k", 0)
 
 
+@pytest.mark.parametrize("B", [1, 3, 9])
+def test_suppressed_column_zero_leaves_no_nan(tiny, B):
+    """suppress=[0] writes -inf into column 0, the first column the row kernels' thread 0 folds (dev_common.h lse_add:
+    a -inf value contributes nothing): every log-probability and every alternative's value is finite or -inf"""
+    _, c = tiny
+    pcms = clips(B)
+    c.set_option("token_logprobs", 1)
+    c.set_option("top_k", 4)
+    try:
+        turn_on(c, suppress=[0])
+        r = c.transcribe(pcms, max_tokens=6, ignore_eos=True)
+    finally:
+        c.set_constraints()
+        c.set_option("token_logprobs", 0)
+        c.set_option("top_k", 0)
+    for b in range(B):
+        lp, (tid, tlp) = np.asarray(r.logprobs[b], f32), r.topk[b]
+        assert len(lp) == 6 and not np.isnan(lp).any() and np.isfinite(lp).all(), (b, lp)
+        assert not np.isnan(np.asarray(tlp)).any() and (np.isfinite(tlp) | np.isneginf(tlp)).all(), (b, tlp)
+        assert 0 not in r.tokens[b] and not (np.asarray(tid) == 0).any(), (b, r.tokens[b])
+
+
 # -------------------------------------------------------- the effect is real
 def test_no_repeat_ends_the_loop_and_suppress_removes_a_token(tiny):
     _, c = tiny
