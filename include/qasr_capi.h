@@ -304,6 +304,18 @@ int qasr_get_step_logprobs(qasr_ctx *c, float *out, int B);
 int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens);
 int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap);
 
+/* ---- decode steps of 2 .. 8 rows on the matrix units ------------------------ */
+/* Context option "gemv_rows" [QASR_GEMV_ROWS], f16 models: which kernel runs the
+ * QKV, o, gate/up and down projections of a decode step of 2 .. 8 rows (beam
+ * search, n-best, scoring of a few hypotheses, small batches).  0: the vector-ALU
+ * GEMVs only.  1 (default): the MFMA weight-streaming GEMV (csrc/gemv_rows.hip)
+ * in decoders with hidden >= 2048, at the (projection, rows) pairs where it
+ * measured faster; smaller decoders launch what they always did.  2: wherever
+ * that kernel covers the launch (tests, A/B runs).  Other values: QASR_ERR_ARG.
+ * Results differ between the settings by fp32 summation order only; every
+ * setting is bit-reproducible.  Read-only "gemv_rows_path": the projections of
+ * layer 0 the last emitted step ran on it (bit 0 QKV, 1 o, 2 gate/up, 3 down). */
+
 /* ---- top-K token alternatives (no reference counterpart) ------------------- */
 /* Context option "top_k" [QASR_TOP_K], 0 .. QASR_TOPK_MAX, default 0 (a value
  * outside the range is QASR_ERR_ARG): with K > 0 every greedy step also yields,
@@ -643,6 +655,10 @@ typedef struct {
 int qasr_kt_gemv(int device, qasr_kt_gemv_args *a);
 /* the same arrays, guards and reporting through launch_gemv_wide (f16 W, 4096 < K <= 8192) */
 int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a);
+/* the same through launch_gemv_rows (f16 W, 2 <= M <= 8, K % 256 == 0, 256 <= K <= 8192).  res == out_f32 (one
+ * host array, ldr == ldo): the launch runs in place -- the array is the whole output allocation (guard rows
+ * included), its rows behind the leading guard rows hold the residual on entry and the result on return */
+int qasr_kt_gemv_rows(int device, qasr_kt_gemv_args *a);
 
 typedef struct {
     int32_t M, K, ldx, gather_C, guard;

@@ -70,6 +70,7 @@ static const std::vector<FuseOption> &fuse_options() {
         {"beam_width", "QASR_BEAM_WIDTH", &FuseCfg::beam_width},
         {"sample_slices", "QASR_SAMPLE_SLICES", &FuseCfg::sample_slices},
         {"align_monotone", "QASR_ALIGN_MONOTONE", &FuseCfg::align_monotone},
+        {"gemv_rows", "QASR_GEMV_ROWS", &FuseCfg::gemv_rows},
     };
     return v;
 }
@@ -371,6 +372,7 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
             if (n == "top_k" && (value < 0 || value > QASR_TOPK_MAX)) return fail(QASR_ERR_ARG, "top_k out of range (0..8)");
             if (n == "beam_width" && (value < 0 || value > QASR_BEAM_MAX)) return fail(QASR_ERR_ARG, "beam_width out of range (0..8)");
             if (n == "align_monotone" && value != 0 && value != 1) return fail(QASR_ERR_ARG, "align_monotone is 0 or 1");
+            if (n == "gemv_rows" && (value < 0 || value > 2)) return fail(QASR_ERR_ARG, "gemv_rows is 0, 1 or 2");
             if (n == "sample_slices" && value < 0) return fail(QASR_ERR_ARG, "sample_slices must be >= 0");
             if (n == "beam_width" && value >= 2) {
                 HIPCHK(hipSetDevice(c->m->device));
@@ -416,6 +418,7 @@ extern "C" int qasr_ctx_get_option(const qasr_ctx *c, const char *name, int *val
     if (n == "fused_mode") { *value = c->last_fmode; return 0; }
     if (n == "fused_exact") { *value = c->last_fx; return 0; }
     if (n == "attn_path") { *value = c->last_attn; return 0; }
+    if (n == "gemv_rows_path") { *value = c->last_rows; return 0; }
     if (n == "graph_captures") { *value = (int)c->n_captures; return 0; }
     if (n == "slots_qkv") { *value = std::min(c->fuse.slots_qkv64, c->fuse.slots_qkv128); return 0; }
     for (const auto &o : fuse_options())

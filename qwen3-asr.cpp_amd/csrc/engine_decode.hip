@@ -23,10 +23,27 @@ static void dec_gemm(qasr_ctx *c, int epi, GemmArgs g, hipStream_t s) {
     launch_gemm(AM_DENSE, epi, g, s);
 }
 
-// batch <= 8 o / down projections: f16 rows longer than launch_gemv takes (the 6144-wide down projection of a
-// hidden-2048 decoder) on the K-split GEMV (gemv_wide.hip), everything else on launch_gemv as before
-static void dec_gemv(const GemvArgs &g, hipStream_t s) {
-    if (g.Wd || g.K <= 4096) return launch_gemv(EPI_F32, g, s);
+// batch <= 8 layer projections, the one place that chooses their kernel.  `which`: 0 QKV, 1 o, 2 gate/up, 3 down.
+//   launch_gemv_rows   2 .. 8 rows of an f16 model on the matrix units (gemv_rows.hip), by option gemv_rows:
+//                      0 never; 1 in decoders with hidden >= 2048, at the (launch, rows) pairs of kRowsAuto;
+//                      2 wherever the launcher covers (tests, A/B runs)
+//   launch_gemv_wide   f16 rows longer than launch_gemv takes (the 6144-wide down projection of a hidden-2048 decoder)
+//   launch_gemv        everything else, as before
+// kRowsAuto[which]: bit M set = at M rows the MFMA kernel measured faster than what ran before on the 1.7B shape of
+// that launch (tools/micro/gemv_rows_bench.hip, profiles/gemv_rows/micro.txt).  Measured at 2, 4 and
+// 8 rows; 3 rows follow 4 and 5 .. 7 follow 8: the kernels before it are instantiated for 2, 4 and 8 rows and cost
+// what the next size up costs, the MFMA kernel no more than at the next size up.  QKV and gate/up: from 3 rows; o:
+// from 5; down: never (the K-split GEMV won or tied at every row count)
+static constexpr unsigned kRowsAuto[4] = {0x1f8, 0x1e0, 0x1f8, 0};
+static void dec_gemv(qasr_ctx *c, int which, int l, int epi, const GemvArgs &g, hipStream_t s) {
+    const int mode = c->fuse.gemv_rows;
+    const bool rows = mode >= 2 || (mode == 1 && c->m->hp.hidden >= 2048 && (kRowsAuto[which] >> g.M & 1));
+    if (l == 0) c->last_rows &= ~(1 << which);
+    if (rows && gemv_rows_covers(epi, g) && launch_gemv_rows(epi, g, s)) {
+        if (l == 0) c->last_rows |= 1 << which;
+        return;
+    }
+    if (g.Wd || g.K <= 4096 || epi != EPI_F32) return launch_gemv(epi, g, s);
     if (!launch_gemv_wide(EPI_F32, g, s)) note_declined_shape("launch_gemv_wide", g.M, g.N, g.K);
 }
 
@@ -58,6 +75,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     hipStream_t s = c->st;
     float *x = c->d_x;
     const bool skinny = B <= 8;
+    if (!skinny) c->last_rows = 0;
     // decode batches: the LM head as one launch (lmhead.hip's shape conditions)
     const bool lmh_one = !skinny && B <= 128 && c->fuse.lmh && H == 1024 && hp.vocab % 16 == 0;
     // option token_logprobs: inside the one-launch LM head, else from the fp32 logits after the bookkeeping
@@ -168,7 +186,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
                 (void)launch_qkv_attention1(q1, da, &o, c->fuse, s, false);
             } else {
                 if (skinny) {
-                    if (!(skip & 1)) launch_gemv(EPI_F32, q1, s);
+                    if (!(skip & 1)) dec_gemv(c, 0, l, EPI_F32, q1, s);
                 } else {
                     GemmArgs q{};
                     q.M = B; q.N = QD + 2 * KD; q.K = H; q.out_f32 = c->d_qkv; q.ldo = QD + 2 * KD;
@@ -199,11 +217,11 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         }
         if (!gb) continue;
         if (skinny) {
-            if (!o_fused && !(skip & 4)) dec_gemv(o, s);
+            if (!o_fused && !(skip & 4)) dec_gemv(c, 1, l, EPI_F32, o, s);
             if (o_fused) dn.zero8 = att_done;   // re-arm the fused o-proj's arrival counters
             if (skip & 24 || nl < 2 || !launch_ffn1(gu, dn, fcnt, fcnt_next, c->fuse, s)) {
-                if (!(skip & 8)) launch_gemv(q8 ? EPI_SWIGLU_F32 : EPI_SWIGLU_F16, gu, s);
-                if (!(skip & 16)) dec_gemv(dn, s);
+                if (!(skip & 8)) dec_gemv(c, 2, l, q8 ? EPI_SWIGLU_F32 : EPI_SWIGLU_F16, gu, s);
+                if (!(skip & 16)) dec_gemv(c, 3, l, EPI_F32, dn, s);
                 else if (o_fused) (void)hipMemsetAsync(att_done, 0, 8 * 16 * 4, s);   // the skipped down-proj re-arms these
             }
         } else if (q8) {

@@ -316,6 +316,8 @@ struct qasr_ctx {
     int last_attn = 0;             // the same step's decode attention launches (option "attn_path", read-only): 0 split-K
                                    // fp32, 1 chain role of the fused launch, 2 scores + chain in one launch per sequence
                                    // (decode_attn_seq_kernel), 3 separate scores and chain kernels
+    int last_rows = 0;             // the same step, layer 0: which batch <= 8 projections launch_gemv_rows took (option
+                                   // "gemv_rows_path", read-only): bit 0 QKV, 1 o, 2 gate/up, 3 down
     double probe_ms = 0.0, probe_bytes = 0.0, probe_dev_ms = 0.0;
     long probe_dev_n = 0;
     unsigned long long *d_pstamp = nullptr;   // per decode step: [32 min-starts | 32 max-ends] of the probed launches

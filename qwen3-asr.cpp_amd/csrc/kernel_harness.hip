@@ -160,8 +160,11 @@ extern "C" int qasr_kt_gemm(int device, qasr_kt_gemm_args *a) {
     return 0;
 }
 
-// launch_gemv (wide = false) or launch_gemv_wide on the same arrays, guards and reporting
-static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
+// launch_gemv (which = 0), launch_gemv_wide (1) or launch_gemv_rows (2) on the same arrays, guards and reporting.
+// launch_gemv_rows with res == out_f32 (the same host array, ldr == ldo): in place, as the decode step runs its o
+// and down projections -- the output allocation's rows start as the residual rows, its guards as ever
+static int kt_gemv(int device, qasr_kt_gemv_args *a, int which) {
+    const bool inplace = which == 2 && a && a->res && a->res == a->out_f32 && a->ldr == a->ldo;
     if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || a->wrows < a->N)
         return fail(QASR_ERR_ARG, "bad arguments");
     if (!(a->Wq ? a->Wd != nullptr : a->W != nullptr) || !(a->x || a->xh || (a->embd_ids && a->embd)))
@@ -176,7 +179,7 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
     if ((rc = put_in(x, a->x, M, a->ldx, 4, G, 0xFF)) || (rc = put_in(xh, a->xh, M, a->ldxh, 2, G, 0xFF)) ||
         (rc = put_in(nw, a->norm_w, 1, K, 4, 1, 0xFF)) || (rc = put_in(W, a->W, a->wrows, K, 2, G, 0xFF)) ||
         (rc = put_in(Wq, a->Wq, a->wrows, K, 1, G, 0x7F)) || (rc = put_in(Wd, a->Wd, a->wrows, K / 32, 2, G, 0xFF)) ||
-        (rc = put_in(bias, a->bias, 1, N, 4, 1, 0xFF)) || (rc = put_in(res, a->res, M, a->ldr, 4, G, 0xFF)) ||
+        (rc = put_in(bias, a->bias, 1, N, 4, 1, 0xFF)) || (rc = put_in(res, inplace ? nullptr : a->res, M, a->ldr, 4, G, 0xFF)) ||
         (rc = put_in(ids, a->embd_ids, 1, M, 4, 0, 0)) || (rc = put_in(embd, a->embd, a->embd_rows, K, 2, G, 0xFF)) ||
         (rc = put_out(xs, a->x_store, M, a->ldx, 4, G)) || (rc = put_out(o32, a->out_f32, M, a->ldo, 4, G)) ||
         (rc = put_out(o16, a->out_f16, M, a->ldo16, 2, G)) || (rc = put_state(amax, a->amax, 8 * 8)) ||
@@ -195,6 +198,10 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
     g.bias = bias.ptr<float>();
     g.res = res.ptr<float>(); g.ldr = a->ldr;
     g.out_f32 = o32.ptr<float>(); g.ldo = a->ldo;
+    if (inplace) {   // the host array is the whole allocation: its rows behind the guard rows are the residual
+        HIPCHK(hipMemcpy(o32.ptr<float>(), (const char *)a->res + o32.off, (size_t)M * a->ldo * 4, hipMemcpyHostToDevice));
+        g.res = o32.ptr<float>();
+    }
     g.out_f16 = o16.ptr<uint16_t>(); g.ldo16 = a->ldo16;
     g.amax = amax.ptr<unsigned long long>();
     g.embd_ids = ids.ptr<int32_t>(); g.embd = embd.ptr<uint16_t>(); g.x_store = xs.ptr<float>();
@@ -203,7 +210,8 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
 
     bool ran = true;
     for (int i = 0; i < a->launches; i++) {
-        if (wide) ran = launch_gemv_wide(a->epi, g, nullptr) && ran;
+        if (which == 2) ran = launch_gemv_rows(a->epi, g, nullptr) && ran;
+        else if (which == 1) ran = launch_gemv_wide(a->epi, g, nullptr) && ran;
         else launch_gemv(a->epi, g, nullptr);
         if (i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
     }
@@ -215,8 +223,9 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, bool wide) {
     return 0;
 }
 
-extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, false); }
-extern "C" int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, true); }
+extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 0); }
+extern "C" int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 1); }
+extern "C" int qasr_kt_gemv_rows(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 2); }
 
 extern "C" int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a) {
     if (!a || a->M <= 0 || a->K <= 0 || a->K % 32 != 0 || a->guard < 0 || !a->q || !a->d || !a->x32 == !a->x16 || a->gather_C < 0)

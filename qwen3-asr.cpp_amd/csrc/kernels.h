@@ -190,6 +190,10 @@ struct GemmArgs {
 //   launch_gemv_wide        f16 W rows K apart, 1 <= M <= 8, K in {6144, 8192} (4096 < K <= 8192, K % 2048 == 0),
 //                           xh (ldxh % 8 == 0) or x (ldx % 4 == 0); EPI_F32 (+ bias, + res, out_f32 may be res)
 //                           and EPI_F16 (+ bias); no Wd / norm_w / embd_ids / amax   -- returns false otherwise
+//   launch_gemv_rows        f16 W rows K apart, 2 <= M <= 8, K % 256 == 0, 256 <= K <= 8192, any N; x (ldx % 4 == 0;
+//                           + norm_w, + embd_ids / embd / x_store) or xh (ldxh % 8 == 0); EPI_F32 (+ bias, + res,
+//                           out_f32 may be res), EPI_F16 (+ bias), EPI_SWIGLU_F16 (N % 16 == 0, the 16-row gate / up
+//                           interleave); no Wd / amax / EPI_ARGMAX   -- recorded as declined and returns false otherwise
 void launch_gemm(int amode, int epi, const GemmArgs &g, hipStream_t s);
 // an unsupported (mode, epilogue) pair or shape launches nothing and is recorded
 // for the calling host thread; take_declined returns (and clears) it -- the
@@ -291,6 +295,12 @@ bool launch_gemv1(int epi, const GemvArgs &g, hipStream_t s);
 // gemv_wide.hip: the rows launch_gemv does not take (f16, 4096 < K <= 8192): a workgroup's four waves
 // split K and add their partial sums in wave order; false = shape not taken, nothing launched
 bool launch_gemv_wide(int epi, const GemvArgs &g, hipStream_t s);
+// gemv_rows.hip: 2 .. 8 rows on v_mfma_f32_16x16x32_f16, the weights streamed from global memory straight into the
+// A operand (the coverage rule stands above the launcher and in the table above).  A launch outside it is recorded
+// (note_declined / note_declined_shape), launches nothing and returns false; gemv_rows_covers is that rule alone
+// (the decode step asks it before it chooses, so a fall-back records nothing)
+bool gemv_rows_covers(int epi, const GemvArgs &g);
+bool launch_gemv_rows(int epi, const GemvArgs &g, hipStream_t s);
 
 // Batch-1 fused launches (a role waits in-launch on another role's output):
 // per-context switches, delays and the device's co-residency capacity.  Every
@@ -371,6 +381,9 @@ struct FuseCfg {
     int align_monotone = 0;             // aligner models: qasr_align_json* take the monotone path over the classify
                                         // head's fp32 logits (align_path.hip) and add the log-probabilities of the
                                         // boundaries; 0: nothing changes
+    int gemv_rows = 1;                  // batch 2 .. 8, f16 models: the layer projections on the MFMA weight-streaming GEMV
+                                        // (gemv_rows.hip): 0 never, 1 in decoders with hidden >= 2048 at the (launch, rows)
+                                        // pairs where it measured faster (engine_decode.hip kRowsAuto), 2 wherever it covers
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
