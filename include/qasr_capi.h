@@ -305,10 +305,11 @@ int qasr_get_logprobs(qasr_ctx *c, float *out, int B, int max_tokens);
 int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap);
 
 /* ---- decode steps of 2 .. 8 rows on the matrix units ------------------------ */
-/* Context option "gemv_rows" [QASR_GEMV_ROWS], f16 models: which kernel runs the
- * QKV, o, gate/up and down projections of a decode step of 2 .. 8 rows (beam
- * search, n-best, scoring of a few hypotheses, small batches).  0: the vector-ALU
- * GEMVs only.  1 (default): the MFMA weight-streaming GEMV (csrc/gemv_rows.hip)
+/* Context option "gemv_rows" [QASR_GEMV_ROWS], f16 and Q8_0 models: which kernel
+ * runs the QKV, o, gate/up and down projections of a decode step of 2 .. 8 rows
+ * (beam search, n-best, scoring of a few hypotheses, small batches).  0: the
+ * vector-ALU GEMVs only.  1 (default): the MFMA weight-streaming GEMV
+ * (csrc/gemv_rows.hip for f16 weights, csrc/gemv_rows_q8.hip for Q8_0 weights)
  * in decoders with hidden >= 2048, at the (projection, rows) pairs where it
  * measured faster; smaller decoders launch what they always did.  2: wherever
  * that kernel covers the launch (tests, A/B runs).  Other values: QASR_ERR_ARG.
@@ -659,6 +660,9 @@ int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a);
  * host array, ldr == ldo): the launch runs in place -- the array is the whole output allocation (guard rows
  * included), its rows behind the leading guard rows hold the residual on entry and the result on return */
 int qasr_kt_gemv_rows(int device, qasr_kt_gemv_args *a);
+/* the same, in place likewise, through launch_gemv_rows_q8 (Q8_0 Wq / Wd, fp32 x, 2 <= M <= 8, K % 256 == 0,
+ * 256 <= K <= 8192; EPI_F32 and EPI_SWIGLU_F32) */
+int qasr_kt_gemv_rows_q8(int device, qasr_kt_gemv_args *a);
 
 typedef struct {
     int32_t M, K, ldx, gather_C, guard;

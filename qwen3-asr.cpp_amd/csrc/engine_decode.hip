@@ -24,7 +24,8 @@ static void dec_gemm(qasr_ctx *c, int epi, GemmArgs g, hipStream_t s) {
 }
 
 // batch <= 8 layer projections, the one place that chooses their kernel.  `which`: 0 QKV, 1 o, 2 gate/up, 3 down.
-//   launch_gemv_rows   2 .. 8 rows of an f16 model on the matrix units (gemv_rows.hip), by option gemv_rows:
+//   launch_gemv_rows   2 .. 8 rows of an f16 model on the matrix units (gemv_rows.hip; a Q8_0 model: launch_gemv_rows_q8,
+//                      gemv_rows_q8.hip, by kRowsAutoQ8), by option gemv_rows:
 //                      0 never; 1 in decoders with hidden >= 2048, at the (launch, rows) pairs of kRowsAuto;
 //                      2 wherever the launcher covers (tests, A/B runs)
 //   launch_gemv_wide   f16 rows longer than launch_gemv takes (the 6144-wide down projection of a hidden-2048 decoder)
@@ -35,11 +36,18 @@ static void dec_gemm(qasr_ctx *c, int epi, GemmArgs g, hipStream_t s) {
 // what the next size up costs, the MFMA kernel no more than at the next size up.  QKV and gate/up: from 3 rows; o:
 // from 5; down: never (the K-split GEMV won or tied at every row count)
 static constexpr unsigned kRowsAuto[4] = {0x1f8, 0x1e0, 0x1f8, 0};
+// the same for a Q8_0 model (g.Wd set): launch_gemv_rows_q8 (gemv_rows_q8.hip) against launch_gemv's gemv_q8_kernel,
+// which also runs the 6144-wide down projection (tools/micro/gemv_rows_q8_bench.hip, profiles/gemv_rows_q8/micro.txt;
+// DESIGN.md 5.13).  On the 1.7B shapes it lost at 2 and 4 rows at all four launches (1.02 .. 1.48 x) and won at 8
+// (QKV 0.95, o 0.82, gate/up 0.64, down 0.89 x): from 5 rows everywhere, the 3-row and 5 .. 7-row entries by the rule above
+static constexpr unsigned kRowsAutoQ8[4] = {0x1e0, 0x1e0, 0x1e0, 0x1e0};
 static void dec_gemv(qasr_ctx *c, int which, int l, int epi, const GemvArgs &g, hipStream_t s) {
     const int mode = c->fuse.gemv_rows;
-    const bool rows = mode >= 2 || (mode == 1 && c->m->hp.hidden >= 2048 && (kRowsAuto[which] >> g.M & 1));
+    const bool q8 = g.Wd != nullptr;
+    const bool rows = mode >= 2 || (mode == 1 && c->m->hp.hidden >= 2048 && ((q8 ? kRowsAutoQ8 : kRowsAuto)[which] >> g.M & 1));
     if (l == 0) c->last_rows &= ~(1 << which);
-    if (rows && gemv_rows_covers(epi, g) && launch_gemv_rows(epi, g, s)) {
+    if (rows && (q8 ? gemv_rows_q8_covers(epi, g) && launch_gemv_rows_q8(epi, g, s)
+                    : gemv_rows_covers(epi, g) && launch_gemv_rows(epi, g, s))) {
         if (l == 0) c->last_rows |= 1 << which;
         return;
     }

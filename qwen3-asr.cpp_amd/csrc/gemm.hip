@@ -19,6 +19,7 @@
 #include "gemm_epi.h"
 #include "gemm8p.h"
 #include "gemm_glds.h"
+#include "q8_prologue.h"
 
 namespace qasr {
 
@@ -580,8 +581,8 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(GemvArgs g) {
     if (cg < ncg) wload(cg);
     // ---- prologue: each thread owns 4 consecutive elements per 1024-wide pass
     constexpr int KP = NK;
-    {
-        float xr[MR][KP][4];
+    {   // q8_prologue.h: the arithmetic and the thread-to-element map
+        float4 xr[MR][KP];
         double ss[MR];
 #pragma unroll
         for (int m = 0; m < MR; m++) {
@@ -589,21 +590,8 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(GemvArgs g) {
 #pragma unroll
             for (int p = 0; p < KP; p++) {
                 const int k = p * 1024 + tid * 4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (m < g.M && k < K) {
-                    if (g.embd_ids) {
-                        const uint2 hv = *(const uint2 *)(g.embd + (long)g.embd_ids[m] * K + k);
-                        v = make_float4(u16_to_f(hv.x & 0xffff), u16_to_f(hv.x >> 16), u16_to_f(hv.y & 0xffff), u16_to_f(hv.y >> 16));
-                        if (g.x_store && blockIdx.x == 0) *(float4 *)(g.x_store + (long)m * g.ldx + k) = v;
-                    } else {
-                        v = *(const float4 *)(g.x + (long)m * g.ldx + k);
-                    }
-                }
-                xr[m][p][0] = v.x; xr[m][p][1] = v.y; xr[m][p][2] = v.z; xr[m][p][3] = v.w;
-                ss[m] += (double)(v.x * v.x);
-                ss[m] += (double)(v.y * v.y);
-                ss[m] += (double)(v.z * v.z);
-                ss[m] += (double)(v.w * v.w);
+                xr[m][p] = m < g.M && k < K ? q8p_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                q8p_sq(ss[m], xr[m][p]);
             }
         }
         if (g.norm_w) {
@@ -616,33 +604,15 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(GemvArgs g) {
         }
 #pragma unroll
         for (int m = 0; m < MR; m++) {
-            float scale = 1.0f;
-            if (g.norm_w) {
-                const double tot = red[0][m] + red[1][m] + red[2][m] + red[3][m];
-                scale = 1.0f / sqrtf((float)(tot / K) + g.eps);
-            }
+            const float scale = q8p_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
 #pragma unroll
             for (int p = 0; p < KP; p++) {
                 const int k = p * 1024 + tid * 4;
-                float v[4], amax = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    v[e] = xr[m][p][e];
-                    if (g.norm_w && k < K) v[e] = fmul_rn(fmul_rn(v[e], scale), g.norm_w[k + e]);
-                    if (m >= g.M) v[e] = 0.0f;
-                    amax = fmaxf(amax, fabsf(v[e]));
-                }
-                // block of 32 = 8 consecutive lanes (quantize_row_q8_0)
-                amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-                amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-                amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+                float d;
+                const uint32_t u = q8p_quant(g, xr[m][p], k, scale, m < g.M && k < K, d);
                 if (k < K) {
-                    const float id = amax != 0.0f ? 127.f / amax : 0.0f;
-                    uint32_t u = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) u |= (uint32_t)(uint8_t)(int8_t)__builtin_rintf(fmul_rn(v[e], id)) << (8 * e);
                     *(uint32_t *)(xq + m * K + k) = u;
-                    if ((tid & 7) == 0) xd[m * nb + (k >> 5)] = u16_to_f(f_to_u16(amax / 127.f));
+                    if ((tid & 7) == 0) xd[m * nb + (k >> 5)] = d;
                 }
             }
         }

@@ -160,11 +160,11 @@ extern "C" int qasr_kt_gemm(int device, qasr_kt_gemm_args *a) {
     return 0;
 }
 
-// launch_gemv (which = 0), launch_gemv_wide (1) or launch_gemv_rows (2) on the same arrays, guards and reporting.
-// launch_gemv_rows with res == out_f32 (the same host array, ldr == ldo): in place, as the decode step runs its o
+// launch_gemv (which = 0), launch_gemv_wide (1), launch_gemv_rows (2) or launch_gemv_rows_q8 (3) on the same arrays,
+// guards and reporting.  launch_gemv_rows / _q8 with res == out_f32 (the same host array, ldr == ldo): in place, as the decode step runs its o
 // and down projections -- the output allocation's rows start as the residual rows, its guards as ever
 static int kt_gemv(int device, qasr_kt_gemv_args *a, int which) {
-    const bool inplace = which == 2 && a && a->res && a->res == a->out_f32 && a->ldr == a->ldo;
+    const bool inplace = which >= 2 && a && a->res && a->res == a->out_f32 && a->ldr == a->ldo;
     if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->guard < 0 || a->launches < 1 || a->wrows < a->N)
         return fail(QASR_ERR_ARG, "bad arguments");
     if (!(a->Wq ? a->Wd != nullptr : a->W != nullptr) || !(a->x || a->xh || (a->embd_ids && a->embd)))
@@ -210,7 +210,8 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, int which) {
 
     bool ran = true;
     for (int i = 0; i < a->launches; i++) {
-        if (which == 2) ran = launch_gemv_rows(a->epi, g, nullptr) && ran;
+        if (which == 3) ran = launch_gemv_rows_q8(a->epi, g, nullptr) && ran;
+        else if (which == 2) ran = launch_gemv_rows(a->epi, g, nullptr) && ran;
         else if (which == 1) ran = launch_gemv_wide(a->epi, g, nullptr) && ran;
         else launch_gemv(a->epi, g, nullptr);
         if (i + 1 < a->launches) HIPCHK(hipDeviceSynchronize());
@@ -226,6 +227,7 @@ static int kt_gemv(int device, qasr_kt_gemv_args *a, int which) {
 extern "C" int qasr_kt_gemv(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 0); }
 extern "C" int qasr_kt_gemv_wide(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 1); }
 extern "C" int qasr_kt_gemv_rows(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 2); }
+extern "C" int qasr_kt_gemv_rows_q8(int device, qasr_kt_gemv_args *a) { return kt_gemv(device, a, 3); }
 
 extern "C" int qasr_kt_quantize_q8(int device, qasr_kt_quant_args *a) {
     if (!a || a->M <= 0 || a->K <= 0 || a->K % 32 != 0 || a->guard < 0 || !a->q || !a->d || !a->x32 == !a->x16 || a->gather_C < 0)

@@ -194,6 +194,10 @@ struct GemmArgs {
 //                           + norm_w, + embd_ids / embd / x_store) or xh (ldxh % 8 == 0); EPI_F32 (+ bias, + res,
 //                           out_f32 may be res), EPI_F16 (+ bias), EPI_SWIGLU_F16 (N % 16 == 0, the 16-row gate / up
 //                           interleave); no Wd / amax / EPI_ARGMAX   -- recorded as declined and returns false otherwise
+//   launch_gemv_rows_q8     Q8_0 W (int8 rows K apart + Wd), 2 <= M <= 8, K % 256 == 0, 256 <= K <= 8192, any N; x
+//                           (ldx % 4 == 0; + norm_w, + embd_ids / embd / x_store); EPI_F32 (+ bias, + res, out_f32 may
+//                           be res), EPI_SWIGLU_F32 (N % 16 == 0, the 16-row gate / up interleave); no xh / amax /
+//                           EPI_ARGMAX / fp16 outputs   -- recorded as declined and returns false otherwise
 void launch_gemm(int amode, int epi, const GemmArgs &g, hipStream_t s);
 // an unsupported (mode, epilogue) pair or shape launches nothing and is recorded
 // for the calling host thread; take_declined returns (and clears) it -- the
@@ -301,6 +305,11 @@ bool launch_gemv_wide(int epi, const GemvArgs &g, hipStream_t s);
 // (the decode step asks it before it chooses, so a fall-back records nothing)
 bool gemv_rows_covers(int epi, const GemvArgs &g);
 bool launch_gemv_rows(int epi, const GemvArgs &g, hipStream_t s);
+// gemv_rows_q8.hip: the same for Q8_0 weights, on v_mfma_i32_16x16x64_i8 (one block's exact integer dots an MFMA),
+// the rows normed and quantised in the launch with gemv_q8_kernel's prologue (q8_prologue.h): launch_gemv's products
+// in another fp32 summation order.  Declines and gemv_rows_q8_covers as above
+bool gemv_rows_q8_covers(int epi, const GemvArgs &g);
+bool launch_gemv_rows_q8(int epi, const GemvArgs &g, hipStream_t s);
 
 // Batch-1 fused launches (a role waits in-launch on another role's output):
 // per-context switches, delays and the device's co-residency capacity.  Every
@@ -381,9 +390,10 @@ struct FuseCfg {
     int align_monotone = 0;             // aligner models: qasr_align_json* take the monotone path over the classify
                                         // head's fp32 logits (align_path.hip) and add the log-probabilities of the
                                         // boundaries; 0: nothing changes
-    int gemv_rows = 1;                  // batch 2 .. 8, f16 models: the layer projections on the MFMA weight-streaming GEMV
-                                        // (gemv_rows.hip): 0 never, 1 in decoders with hidden >= 2048 at the (launch, rows)
-                                        // pairs where it measured faster (engine_decode.hip kRowsAuto), 2 wherever it covers
+    int gemv_rows = 1;                  // batch 2 .. 8, f16 and Q8_0 models: the layer projections on the MFMA weight-streaming
+                                        // GEMV (gemv_rows.hip / gemv_rows_q8.hip): 0 never, 1 in decoders with hidden >= 2048 at
+                                        // the (launch, rows) pairs where it measured faster (engine_decode.hip kRowsAuto /
+                                        // kRowsAutoQ8), 2 wherever it covers
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
