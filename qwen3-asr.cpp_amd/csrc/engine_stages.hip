@@ -474,6 +474,7 @@ struct qasr_mel_engine {
     double *hann = nullptr;
     float *filt = nullptr;        // [128][201], the last filterbank run with
     std::vector<float> filt_host; // ... its host copy (re-uploaded when a call brings other values)
+    std::vector<float> filt_builtin;   // generate_mel_filters: what filters = NULL means in every call
     float *pcm = nullptr, *out = nullptr;
     double *tmp = nullptr;
     unsigned long long *cmax = nullptr;
@@ -519,6 +520,7 @@ extern "C" int qasr_mel_engine_create(int device, qasr_mel_engine **out) {
     dft_twiddles(tw);
     hann_window(hn);
     mel_filters(e->filt_host);
+    e->filt_builtin = e->filt_host;
     HIPCHK(hipMalloc((void **)&e->tw, tw.size() * 8));
     HIPCHK(hipMalloc((void **)&e->hann, hn.size() * 8));
     HIPCHK(hipMalloc((void **)&e->filt, e->filt_host.size() * 4));
@@ -537,7 +539,8 @@ extern "C" int qasr_mel_engine_run(qasr_mel_engine *e, const float *pcm, int n, 
     if (!e || n < 0 || (n > 0 && !pcm) || (mel_frames(n) > 0 && !mel_out)) return fail(QASR_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(e->device));
     const int TF = n / 160 + 1, T = TF - 1;
-    if (filters && memcmp(filters, e->filt_host.data(), e->filt_host.size() * 4) != 0) {
+    if (!filters) filters = e->filt_builtin.data();   // (not whatever bank the call before left on the device)
+    if (memcmp(filters, e->filt_host.data(), e->filt_host.size() * 4) != 0) {
         memcpy(e->filt_host.data(), filters, e->filt_host.size() * 4);
         HIPCHK(hipMemcpyAsync(e->filt, e->filt_host.data(), e->filt_host.size() * 4, hipMemcpyHostToDevice, e->st));
     }
