@@ -278,7 +278,11 @@ int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value);
 int qasr_ctx_get_option(const qasr_ctx *c, const char *name, int *value);
 /* diagnostic copy of decode-step state (after qasr_decode_step): "x" fp32
  * [max_batch][hidden] residual stream, "act" fp16 [max_batch][ffn] SwiGLU
- * output, "qkv" fp32 [max_batch][q+k+v], "att" fp16 [max_batch][n_head*128] */
+ * output, "qkv" fp32 [max_batch][q+k+v], "att" fp16 [max_batch][n_head*128].
+ * For the tests, tiny models only: the whole caches "kc" / "vc" fp16 and their
+ * E4M3 shadow "k8" / "v8" uint8, each [dec_layers][max_batch][n_kv_head][max_ctx][128]
+ * (2 and 1 bytes an element); "k8" / "v8" are QASR_ERR_STATE while the shadow
+ * does not exist (option kv_fp8 was never 1) */
 int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64_t bytes);
 
 /* ---- token log-probabilities (no reference counterpart) -------------------- */
@@ -316,6 +320,30 @@ int qasr_stream_logprobs(qasr_ctx *c, float *out, int cap);
  * Results differ between the settings by fp32 summation order only; every
  * setting is bit-reproducible.  Read-only "gemv_rows_path": the projections of
  * layer 0 the last emitted step ran on it (bit 0 QKV, 1 o, 2 gate/up, 3 down). */
+
+/* ---- FP8 shadow KV cache for decode batches (no reference counterpart) ------ */
+/* Context option "kv_fp8" [QASR_KV_FP8], 0 / 1, default 0; other values
+ * QASR_ERR_ARG.  At 1 the context keeps an E4M3 (OCP, no infinities, max 448)
+ * copy of the K and V caches beside them -- half their bytes again, allocated
+ * the first time the option is 1 -- and every decode step of 9 .. 128 rows
+ * runs csrc/kv_fp8.hip's attention kernel on it, whatever "fa_exact_decode",
+ * "att_stream" and "fx_seq" say: the bytes become fp16 in registers and go
+ * through the f16 MFMA scores and fp32 softmax and P.V of fa_exact_decode = 0,
+ * so the numerics are those of fa_exact_decode = 0 on rounded keys and values,
+ * not ggml's fp16-accumulating chain.  The fp16 caches stay the source of
+ * truth: prefills, steps of 1 .. 8 rows and every other kernel read them as
+ * before, and the shadow is re-derived wherever they change (after a prefill,
+ * after a KV fork, once a step of 1 .. 8 rows, when the option turns on), so
+ * beam search, n-best, scoring, streaming and the token callback work with it.
+ * Shapes other than n_head == 2 n_kv_head fall back to the fp16 kernels.
+ * "kv_fp8_exp" [QASR_KV_FP8_EXP], -8 .. 8, default 0: the exponent s of the
+ * rule q = RNE_E4M3FN(clamp(x 2^s, -448, 448)), value used float(q) 2^-s
+ * (csrc/kv_fp8_host.h).  Read-only "kv_fp8_path": 1 if layer 0 of the last
+ * emitted step ran the FP8 kernel.  Aligner models accept and ignore both.
+ * Measured on one MI355X (profiles/kv_fp8; full-size
+ * synthetic f16 model, 30 s clips): the bytes halve by construction; the
+ * attention launch took 0.65 x the fp16 fa_exact_decode = 0 kernel's time at
+ * 128 rows (0.67 x at 64), the decode step 0.82 x (0.87 x). */
 
 /* ---- top-K token alternatives (no reference counterpart) ------------------- */
 /* Context option "top_k" [QASR_TOP_K], 0 .. QASR_TOPK_MAX, default 0 (a value
@@ -1164,6 +1192,42 @@ typedef struct {
     char msg[256];
 } qasr_kt_decode_attention_args;
 int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_args *a);
+
+/* The FP8 shadow KV cache's two kernels (csrc/kv_fp8.hip; tests/kv_fp8_util.py holds the bindings).
+ * qasr_kt_kv_fp8_convert: kv_fp8_convert_kernel on kc / vc fp16 (in) and k8 / v8 uint8 (in / out, whole), each
+ * [layers][slots + guard][n_kv_head][max_ctx][128], the last `guard` slots of every layer guard slots the caller
+ * filled with 0xFF; row b re-derives positions [from[b], to[b]) of slot slot[b] with exponent exp; span: positions the
+ * grid covers from from[b] on (0 = max_ctx).  The shadows sit between fences; a write outside is QASR_ERR_STATE. */
+typedef struct {
+    int32_t layers, n_kv_head, max_ctx, slots, guard, B, span, exp;
+    const int32_t *slot, *from, *to;   /* [B] */
+    const uint16_t *kc, *vc;
+    uint8_t *k8, *v8;
+    int32_t declined;
+} qasr_kt_kv_fp8_convert_args;
+int qasr_kt_kv_fp8_convert(int device, qasr_kt_kv_fp8_convert_args *a);
+/* qasr_kt_decode_attn_fp8: launch_decode_attention_fp8 on qasr_kt_decode_attention's arrays (row b = cache slot b, the
+ * fp16 caches uploaded with their pad rows, in / out between fences) plus the shadows k8 / v8 uint8
+ * [B + guard][n_kv_head][max_ctx][128] in / out between fences, the last `guard` slots guard slots of 0xFF.  repeat 2:
+ * a second launch on the caches and shadows as the caller gave them, into the *_b outputs; both launches must leave
+ * the same caches and shadows.  Before any launch (QASR_ERR_ARG): 0 <= pos[b] < min(max_ctx, max_pos), exactly one
+ * output kind.  tag: "decode_seq_fp8<128>". */
+typedef struct {
+    int32_t B, n_head, n_kv_head, max_ctx, max_pos, kv_nt, exp, repeat, guard;
+    float scale, eps;
+    const int32_t *pos;
+    const float *qkv, *q_norm, *k_norm, *rope;
+    uint16_t *kc, *vc, *vt;
+    uint8_t *k8, *v8;
+    uint16_t *out, *out_b;
+    float *out32, *out32_b;
+    int8_t *outq, *outq_b;
+    float *outd, *outd_b;
+    int32_t declined;
+    char tag[64];
+    char msg[256];
+} qasr_kt_decode_attn_fp8_args;
+int qasr_kt_decode_attn_fp8(int device, qasr_kt_decode_attn_fp8_args *a);
 
 /* The conv front end (tests/conv_util.py holds the bindings).  layer 1: launch_conv1 over mel; 2 / 3: launch_gemm in
  * AM_CONV2 / AM_CONV3 with EPI_GELU_F16, N = C, K = 9 C, ldw = conv_kpad(C) = 9 C rounded up to 128, ldo16 = C,

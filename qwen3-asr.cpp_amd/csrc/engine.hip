@@ -71,6 +71,8 @@ static const std::vector<FuseOption> &fuse_options() {
         {"sample_slices", "QASR_SAMPLE_SLICES", &FuseCfg::sample_slices},
         {"align_monotone", "QASR_ALIGN_MONOTONE", &FuseCfg::align_monotone},
         {"gemv_rows", "QASR_GEMV_ROWS", &FuseCfg::gemv_rows},
+        {"kv_fp8", "QASR_KV_FP8", &FuseCfg::kv_fp8},
+        {"kv_fp8_exp", "QASR_KV_FP8_EXP", &FuseCfg::kv_fp8_exp},
     };
     return v;
 }
@@ -191,6 +193,32 @@ int qasr::eng::ensure_beam(qasr_ctx *c) {
     return 0;
 }
 
+// option kv_fp8: the shadow's two buffers the first time the option is 1 (aligner models: never), then every position of
+// every slot derived from the fp16 caches -- the context may hold keys already, and the exponent may have changed
+int qasr::eng::ensure_kv_fp8(qasr_ctx *c) {
+    if (!kv_fp8_on(c)) return 0;
+    if (!c->v8) {   // (the second of the two: set only once both are)
+        const Hparams &hp = c->m->hp;
+        const size_t n = (size_t)hp.dec_layers * c->max_batch * hp.n_kv_head * c->max_ctx * 128;
+        uint8_t *k = nullptr;
+        int rc;
+        if ((rc = dev_alloc(c, (void **)&k, n)) || (rc = dev_alloc(c, (void **)&c->v8, n))) return rc;
+        c->k8 = k;
+    }
+    return kv_fp8_sync(c, nullptr, nullptr, nullptr, nullptr, c->max_batch, c->max_ctx);
+}
+
+int qasr::eng::kv_fp8_sync(qasr_ctx *c, const int *slot, const int *from, const int *to, const int *len, int B, int span) {
+    if (!kv_fp8_on(c) || !c->k8) return 0;
+    KvFp8ConvertArgs a{};
+    a.kc = c->kc; a.vc = c->vc; a.k8 = c->k8; a.v8 = c->v8;
+    a.layers = c->m->hp.dec_layers; a.slots = c->max_batch; a.n_kv_head = c->m->hp.n_kv_head; a.max_ctx = c->max_ctx;
+    a.slot = slot; a.from = from; a.to = to; a.len = len;
+    a.B = B; a.span = span; a.exp = c->fuse.kv_fp8_exp;
+    if (!launch_kv_fp8_convert(a, c->st)) return fail(QASR_ERR_STATE, "kv_fp8: the conversion launcher declined its shape");
+    return 0;
+}
+
 int qasr::eng::topk_step(qasr_ctx *c, int B) {
     const int K = step_k(c);
     if (K <= 0) return 0;
@@ -282,6 +310,8 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
         if (const char *e = getenv(o.env)) c->fuse.*(o.field) = atoi(e);
     }
     if (c->fuse.top_k < 0 || c->fuse.top_k > QASR_TOPK_MAX) return fail(QASR_ERR_ARG, "QASR_TOP_K out of range (0..8)");
+    if (c->fuse.kv_fp8 < 0 || c->fuse.kv_fp8 > 1 || c->fuse.kv_fp8_exp < kKvFp8ExpMin || c->fuse.kv_fp8_exp > kKvFp8ExpMax)
+        return fail(QASR_ERR_ARG, "QASR_KV_FP8 is 0 or 1, QASR_KV_FP8_EXP -8..8");
     fused_slots(c->fuse);   // co-residency on this context's device
     if (const char *tp = getenv("QASR_DEV_TRACE")) {
         c->trace_path = tp;
@@ -339,6 +369,11 @@ extern "C" int qasr_ctx_create(qasr_model *m, int max_batch, int max_ctx, qasr_c
     c->fuse.err = c->d_err;
     HIPCHK(hipMemset(c->kc, 0, kv * 2));   // decode attention reads whole splits and masks: keep every row finite
     HIPCHK(hipMemset(c->vc, 0, kv * 2));
+    if (kv_fp8_on(c.get())) {   // QASR_KV_FP8=1: the shadow of the zeroed caches (the memsets above ran on the null stream)
+        HIPCHK(hipStreamSynchronize(nullptr));
+        if ((rc = ensure_kv_fp8(c.get()))) return rc;
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
     *out = c.release();
     return 0;
 }
@@ -374,6 +409,8 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
             if (n == "align_monotone" && value != 0 && value != 1) return fail(QASR_ERR_ARG, "align_monotone is 0 or 1");
             if (n == "gemv_rows" && (value < 0 || value > 2)) return fail(QASR_ERR_ARG, "gemv_rows is 0, 1 or 2");
             if (n == "sample_slices" && value < 0) return fail(QASR_ERR_ARG, "sample_slices must be >= 0");
+            if (n == "kv_fp8" && value != 0 && value != 1) return fail(QASR_ERR_ARG, "kv_fp8 is 0 or 1");
+            if (n == "kv_fp8_exp" && (value < kKvFp8ExpMin || value > kKvFp8ExpMax)) return fail(QASR_ERR_ARG, "kv_fp8_exp out of range (-8..8)");
             if (n == "beam_width" && value >= 2) {
                 HIPCHK(hipSetDevice(c->m->device));
                 if (const int rc = ensure_beam(c)) return rc;
@@ -382,6 +419,7 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
                 HIPCHK(hipSetDevice(c->m->device));
                 if (const int rc = ensure_topk(c)) return rc;
             }
+            const int old = c->fuse.*(o.field);
             c->fuse.*(o.field) = value;
             c->drop_graphs();   // captured steps hold the old launch configuration
             if (o.field == &FuseCfg::token_logprobs) {   // nothing has run under the new setting
@@ -400,8 +438,13 @@ extern "C" int qasr_ctx_set_option(qasr_ctx *c, const char *name, int value) {
                 c->tk_run_n.clear();
             }
             HIPCHK(hipSetDevice(c->m->device));   // arrival counters back to rest
-            const int rc = reset_counters(c);
+            int rc = reset_counters(c);
             if (rc) return rc;
+            // the shadow of a context that may already hold keys: derived again when the option turns on (allocating it
+            // the first time) and when the exponent changes under it
+            if (((o.field == &FuseCfg::kv_fp8 && value && !old) || (o.field == &FuseCfg::kv_fp8_exp && value != old)) &&
+                (rc = ensure_kv_fp8(c)))
+                return rc;
             HIPCHK(hipStreamSynchronize(c->st));
             return 0;
         }
@@ -419,6 +462,7 @@ extern "C" int qasr_ctx_get_option(const qasr_ctx *c, const char *name, int *val
     if (n == "fused_exact") { *value = c->last_fx; return 0; }
     if (n == "attn_path") { *value = c->last_attn; return 0; }
     if (n == "gemv_rows_path") { *value = c->last_rows; return 0; }
+    if (n == "kv_fp8_path") { *value = c->last_kv8; return 0; }
     if (n == "graph_captures") { *value = (int)c->n_captures; return 0; }
     if (n == "slots_qkv") { *value = std::min(c->fuse.slots_qkv64, c->fuse.slots_qkv128); return 0; }
     for (const auto &o : fuse_options())
@@ -430,6 +474,7 @@ extern "C" int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64
     if (!c || !buffer || !dst || bytes < 0) return fail(QASR_ERR_ARG, "bad arguments");
     const Hparams &hp = c->m->hp;
     const int64_t B = c->max_batch, QD = hp.n_head * 128, KD = hp.n_kv_head * 128;
+    const int64_t kvn = (int64_t)hp.dec_layers * B * hp.n_kv_head * c->max_ctx * 128;   // elements of a K / V cache
     const std::string n = buffer;
     const void *src = nullptr;
     int64_t cap = 0;
@@ -437,6 +482,12 @@ extern "C" int qasr_debug_read(qasr_ctx *c, const char *buffer, void *dst, int64
     else if (n == "act") { src = c->d_act; cap = B * hp.dec_ffn * 2; }
     else if (n == "qkv") { src = c->d_qkv; cap = B * (QD + 2 * KD) * 4; }
     else if (n == "att") { src = c->d_att; cap = B * QD * 2; }
+    else if (n == "kc" || n == "vc") { src = n == "kc" ? c->kc : c->vc; cap = kvn * 2; }
+    else if (n == "k8" || n == "v8") {
+        if (!c->k8) return fail(QASR_ERR_STATE, "the FP8 shadow does not exist (option kv_fp8 was never 1)");
+        src = n == "k8" ? c->k8 : c->v8;
+        cap = kvn;
+    }
     else if (n == "align_logits") { src = c->alz.p; cap = c->alz_rows * c->m->cls_rows * 4; }   // the last monotone pass's
     else return fail(QASR_ERR_ARG, "unknown buffer '" + n + "'");
     if (bytes > cap) return fail(QASR_ERR_ARG, "read past the buffer");

@@ -38,6 +38,7 @@ extern "C" int qasr_kv_fork(qasr_ctx *c, const int *parent, const int *from, con
     const int *d = c->fork_args.as<int>();
     if (!launch_kv_fork(fork_args(c, d, d + B, d + 2 * B, B, group, (hi + 7) / 8), c->st))
         return fail(QASR_ERR_STATE, "kv_fork: the launcher declined its shape");
+    if (int rc = kv_fp8_sync(c, nullptr, d + B, d + 2 * B, nullptr, B, hi)) return rc;   // option kv_fp8: the forked ranges
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -56,7 +57,8 @@ int qasr::eng::beam_step(qasr_ctx *c, int G, int blocks) {
     a.W = W; a.G = G; a.eos = b.eos;
     if (!launch_beam_select(a, c->st) || !launch_kv_fork(fork_args(c, b.parent, b.from, b.to, G * W, W, blocks), c->st))
         return fail(QASR_ERR_STATE, "beam step: a launcher declined W = " + std::to_string(W));
-    return 0;
+    // option kv_fp8: the forked ranges of the shadow, inside the step graph where the fork is
+    return kv_fp8_sync(c, nullptr, b.from, b.to, nullptr, G * W, blocks * 8);
 }
 
 // --------------------------------------------------------------- beam run

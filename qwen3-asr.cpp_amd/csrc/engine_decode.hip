@@ -107,6 +107,10 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
     int rc;
     const size_t layer_kv = (size_t)c->max_batch * hp.n_kv_head * c->max_ctx * 128;
     const int nl = step_layers(c);   // diagnostic layer cap
+    // option kv_fp8: steps of 9 .. 128 rows attend the E4M3 shadow (decode_attn_seq_fp8_kernel, which writes the
+    // shadow's new rows itself); every other step reads fp16 as before and re-derives its rows of the shadow once,
+    // after the last layer and before the LM head bumps pos
+    const bool kv8_attn = !skinny && kv_fp8_on(c) && c->k8 && decode_attention_fp8_covers(hp.n_head, hp.n_kv_head);
     // probed group (emitted alone): every launch in it folds its block times into one record
     unsigned long long *stamp = r.hi - r.lo == 1 ? c->cur_stamp : nullptr;
     if (r.in(0) && !skinny) launch_embed(c->d_tok, B, m->embd, H, nullptr, nullptr, x, s);
@@ -188,6 +192,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         }
         if (ga) {
             if (l == nl - 1) c->qkv_in_gran = false;
+            if (l == 0) c->last_kv8 = 0;
             if (fmode) {
                 if (c->fuse.gran) { da.gran = c->d_gran; da.layer = l; }
                 if (l == nl - 1) c->qkv_in_gran = c->fuse.gran != 0;
@@ -208,6 +213,8 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
                 }
                 da.att_done = nullptr;
                 if (skip & 2) {
+                } else if (kv8_attn && launch_decode_attention_fp8(da, c->k8 + l * layer_kv, c->v8 + l * layer_kv, c->fuse.kv_fp8_exp, s)) {
+                    if (l == 0) { c->last_attn = 0; c->last_kv8 = 1; }   // (fa_exact_decode = 0's numerics on the rounded keys)
                 } else if (exact) {   // ggml CPU FA numerics: scores by the splits, then the in-order chain
                     da.scores = c->d_scores;
                     da.fx_seq = c->fuse.fx_seq;
@@ -263,6 +270,7 @@ static int decode_step_kernels(qasr_ctx *c, int B, bool want_logits, StepRange r
         }
     }
     if (r.in(1 + 2 * nl)) {
+        if (!kv8_attn && (rc = kv_fp8_sync(c, nullptr, c->d_pos, nullptr, nullptr, B, 1))) return rc;   // position pos[b] of slot b
         if (skinny || lmh_one) {   // the LM head as one launch: the batch <= 8 GEMV, or lmhead.hip at decode batches
             GemvArgs lm{};
             lm.x = x; lm.ldx = H; lm.norm_w = m->out_norm; lm.eps = hp.rms_eps; lm.W = m->embd; lm.K = H; lm.N = hp.vocab; lm.M = B;
@@ -345,8 +353,8 @@ static double probe_bytes(const qasr_ctx *c, int B, int k) {
     const double wb = c->m->q8 ? 34.0 / 32.0 : 2.0;   // bytes per linear weight (Q8_0 block: 34 B / 32)
     if (c->probe == 1) return (double)hp.vocab * H * 2 + B * H * 4 + B * 8.0;
     if (c->probe == 4) {   // the attention launch: K and V^T rows (fp16) + q / k / v rows (fp32) in + output (fp16) out
-        double kv = 0;
-        for (int b = 0; b < B; b++) kv += (double)(c->run_P[b] + k + 1) * KD * 2 * 2;
+        double kv = 0;   // (option kv_fp8: the shadow's K and V rows, one byte an element)
+        for (int b = 0; b < B; b++) kv += (double)(c->run_P[b] + k + 1) * KD * 2 * (c->last_kv8 ? 1 : 2);
         return kv + B * (QD + 2 * KD) * 4 + B * QD * 2;
     }
     if (c->probe == 2) {

@@ -35,6 +35,7 @@
 #include "resample_host.h"
 #include "segment_host.h"
 #include "align_path_host.h"
+#include "kv_fp8_host.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -124,6 +125,10 @@ struct qasr_ctx {
     hipEvent_t ev[EV_COUNT] = {};
     uint16_t *kc = nullptr, *vc = nullptr;
     uint16_t *vt = nullptr;        // V^T cache (kernels.h vt_ctx): the exact decode attention's V
+    // option kv_fp8: the E4M3 shadow of kc / vc in their layout, one byte an element; allocated the
+    // first time the option is 1 (ensure_kv_fp8), null until then
+    uint8_t *k8 = nullptr, *v8 = nullptr;
+    int last_kv8 = 0;              // the last emitted decode step's layer 0 ran decode_attn_seq_fp8_kernel (option "kv_fp8_path")
     float *rope = nullptr;
     std::vector<DevBuf> owned;     // everything hipMalloc'ed by the context
     // grow-on-demand scratch
@@ -376,6 +381,14 @@ int topk_step(qasr_ctx *c, int B);
 inline int step_k(const qasr_ctx *c) { return c->beam_W >= 2 ? c->beam_W : c->fuse.top_k; }
 int ensure_topk(qasr_ctx *c);
 int ensure_beam(qasr_ctx *c);
+// option kv_fp8: on for this context's decoding (aligner models accept the option and never decode)
+inline bool kv_fp8_on(const qasr_ctx *c) { return c->fuse.kv_fp8 != 0 && !c->m->hp.aligner; }
+// the shadow's buffers the first time the option is 1, then the whole shadow re-derived from the fp16 caches
+int ensure_kv_fp8(qasr_ctx *c);
+// after the fp16 caches changed outside the FP8 attention kernel: rows 0 .. B - 1 of the launch re-derive their ranges
+// of the shadow on the context stream (KvFp8ConvertArgs: slot / from / to / len are device arrays or null; span
+// reaches the longest range).  Nothing happens with the option off
+int kv_fp8_sync(qasr_ctx *c, const int *slot, const int *from, const int *to, const int *len, int B, int span);
 // sampling: on for this context's decoding (aligner models ignore it); the rows a prefill draws per sequence; the
 // graph key's first entry (a beam run's width, or 16 x the rows per clip of a sampling step)
 inline bool sampling_on(const qasr_ctx *c) { return c->samp.temperature > 0.f && !c->m->hp.aligner; }

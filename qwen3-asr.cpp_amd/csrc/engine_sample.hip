@@ -184,6 +184,7 @@ int qasr::eng::sample_run(qasr_ctx *c, int max_tokens, int ignore_eos, int32_t *
         const int *d = c->fork_args.as<int>();
         if (!launch_kv_fork(fork_args(c, d, d + B, d + 2 * B, B, N, (maxP + 7) / 8), s))
             return fail(QASR_ERR_STATE, "sampling: the KV-cache fork declined n_best = " + std::to_string(N));
+        if ((rc = kv_fp8_sync(c, nullptr, d + B, d + 2 * B, nullptr, B, maxP))) return rc;   // option kv_fp8: the forked ranges
     }
     if ((rc = decode_graph(c, B, false, maxP)) || (rc = probe_arm(c, max_tokens - 1))) return rc;
     std::vector<int32_t> hist;

@@ -156,6 +156,7 @@ static int score(qasr_ctx *c, const int *clips, const int32_t *tokens, const int
             const int *d = c->fork_args.as<int>();
             if (!launch_kv_fork(fork_args(c, d, d + B, d + 2 * B, B, plan.G, (hi + 7) / 8), st))
                 return fail(QASR_ERR_STATE, "qasr_score: the KV fork declined its shape");
+            if ((rc = kv_fp8_sync(c, nullptr, d + B, d + 2 * B, nullptr, B, hi))) return rc;   // option kv_fp8: the forked ranges
         }
         const std::vector<int> none((size_t)ch.len.size(), -1), zero((size_t)ch.len.size(), 0);
         if ((rc = prefill_layers(c, ch.ids, ch.len, nullptr, none, zero, &ch.slot, &ch.pos0))) return rc;

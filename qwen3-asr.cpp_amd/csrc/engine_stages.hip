@@ -380,6 +380,8 @@ int qasr::eng::prefill_layers(qasr_ctx *c, const std::vector<int32_t> &ids, cons
         dn.M = rows; dn.N = H; dn.K = F; dn.res = x; dn.ldr = H; dn.out_f32 = x; dn.ldo = H;
         linear(c, EPI_F32, dn, x32, c->pact.as<uint16_t>(), F, L.wd, L.wd_d, s);
     }
+    // option kv_fp8: the rows this prefill wrote, positions seq_pos0 .. + seq_len of each sequence's slot
+    if ((rc = kv_fp8_sync(c, d_sslot, d_spos0, nullptr, d_slen, B, maxp))) return rc;
     return declined_check("prefill");
 }
 

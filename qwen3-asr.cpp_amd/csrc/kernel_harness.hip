@@ -942,6 +942,112 @@ extern "C" int qasr_kt_decode_attention(int device, qasr_kt_decode_attention_arg
     return 0;
 }
 
+// ------------------------------------------------------------ FP8 shadow KV cache
+// (tests/test_gpu_kv_fp8_kernel.py) kv_fp8.hip's two kernels; the shadows travel whole, between fences
+extern "C" int qasr_kt_kv_fp8_convert(int device, qasr_kt_kv_fp8_convert_args *a) {
+    if (!a || !a->kc || !a->vc || !a->k8 || !a->v8 || !a->slot || !a->from || !a->to || a->layers <= 0 || a->n_kv_head <= 0 ||
+        a->max_ctx <= 0 || a->slots <= 0 || a->guard < 0 || a->B <= 0 || a->span < 0)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    for (int b = 0; b < a->B; b++)   // (the kernel clamps ranges to [0, max_ctx]; a slot must be a real one)
+        if (a->slot[b] < 0 || a->slot[b] >= a->slots) return fail(QASR_ERR_ARG, "slot outside the caches");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const size_t n = (size_t)a->layers * (a->slots + a->guard) * a->n_kv_head * a->max_ctx * 128;
+    KtBuf kc, vc, sl, frm, to;
+    KtFenced k8, v8;
+    if ((rc = put_state(kc, a->kc, n * 2)) || (rc = put_state(vc, a->vc, n * 2)) || (rc = k8.put(a->k8, n)) || (rc = v8.put(a->v8, n)) ||
+        (rc = put_state(sl, a->slot, (size_t)a->B * 4)) || (rc = put_state(frm, a->from, (size_t)a->B * 4)) ||
+        (rc = put_state(to, a->to, (size_t)a->B * 4)))
+        return rc;
+    KvFp8ConvertArgs f{};
+    f.kc = kc.ptr<uint16_t>(); f.vc = vc.ptr<uint16_t>(); f.k8 = k8.b.ptr<uint8_t>(); f.v8 = v8.b.ptr<uint8_t>();
+    f.layers = a->layers; f.slots = a->slots + a->guard; f.n_kv_head = a->n_kv_head; f.max_ctx = a->max_ctx;
+    f.slot = sl.ptr<int>(); f.from = frm.ptr<int>(); f.to = to.ptr<int>();
+    f.B = a->B; f.span = a->span ? a->span : a->max_ctx; f.exp = a->exp;
+    const bool ran = launch_kv_fp8_convert(f, nullptr);
+    if ((rc = finish_plain(&a->declined, ran))) return rc;
+    if ((rc = k8.take(a->k8, "k8")) || (rc = v8.take(a->v8, "v8"))) return rc;
+    return 0;
+}
+
+extern "C" int qasr_kt_decode_attn_fp8(int device, qasr_kt_decode_attn_fp8_args *a) {
+    if (!a || a->B <= 0 || a->n_head <= 0 || a->n_kv_head <= 0 || a->max_ctx <= 0 || a->max_pos <= 0 || a->guard < 0 || a->repeat < 1 ||
+        a->repeat > 2 || !a->pos || !a->qkv || !a->q_norm || !a->k_norm || !a->rope || !a->kc || !a->vc || !a->vt || !a->k8 || !a->v8)
+        return fail(QASR_ERR_ARG, "bad arguments");
+    const int B = a->B, G = a->guard, nh = a->n_head, nkv = a->n_kv_head;
+    const bool two = a->repeat == 2;
+    if (!a->outq != !a->outd || (a->out != nullptr) + (a->out32 != nullptr) + (a->outq != nullptr) != 1)
+        return fail(QASR_ERR_ARG, "exactly one output kind");
+    if (two && (!a->out != !a->out_b || !a->out32 != !a->out32_b || !a->outq != !a->outq_b || !a->outd != !a->outd_b))
+        return fail(QASR_ERR_ARG, "repeat 2 needs the second output of the same kind");
+    for (int b = 0; b < B; b++)
+        if (a->pos[b] < 0 || a->pos[b] >= std::min(a->max_ctx, a->max_pos)) return fail(QASR_ERR_ARG, "pos outside the caches or the rope table");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int QD = nh * 128, KD = nkv * 128;
+    const size_t kv = (size_t)B * nkv * a->max_ctx * 128 * 2, padded = kv + (size_t)kKvPadRows * 128 * 2;
+    const size_t vtb = (size_t)B * nkv * 128 * vt_ctx(a->max_ctx) * 2, s8 = (size_t)(B + G) * nkv * a->max_ctx * 128;
+    std::vector<unsigned char> hk(padded, 0xFF), hv(padded, 0xFF), k2(padded), v2(padded), first[5], last[5];
+    memcpy(hk.data(), a->kc, kv);
+    memcpy(hv.data(), a->vc, kv);
+    KtBuf qkv, pos, qn, kn, rope, o16[2], o32[2], oq[2], od[2];
+    KtFenced kc, vc, vt, k8, v8;
+    uint16_t *h16[2] = {a->out, a->out_b};
+    float *h32[2] = {a->out32, a->out32_b}, *hd[2] = {a->outd, a->outd_b};
+    int8_t *hq[2] = {a->outq, a->outq_b};
+    if ((rc = put_in(qkv, a->qkv, B, QD + 2 * KD, 4, G, 0xFF)) || (rc = put_in(pos, a->pos, 1, B, 4, 0, 0)) ||
+        (rc = put_in(qn, a->q_norm, 1, 128, 4, 1, 0xFF)) || (rc = put_in(kn, a->k_norm, 1, 128, 4, 1, 0xFF)) ||
+        (rc = put_in(rope, a->rope, a->max_pos, 128, 4, G, 0xFF)) || (rc = kc.put(hk.data(), padded)) || (rc = vc.put(hv.data(), padded)) ||
+        (rc = vt.put(a->vt, vtb)) || (rc = k8.put(a->k8, s8)) || (rc = v8.put(a->v8, s8)))
+        return rc;
+    for (int r = 0; r < a->repeat; r++)
+        if ((rc = put_out(o16[r], h16[r], B, QD, 2, G)) || (rc = put_out(o32[r], h32[r], B, QD, 4, G)) ||
+            (rc = put_out(oq[r], hq[r], B, QD, 1, G)) || (rc = put_out(od[r], hd[r], B, QD / 32, 4, G)))
+            return rc;
+    DecodeAttnArgs d{};
+    d.qkv = qkv.ptr<float>(); d.q_norm = qn.ptr<float>(); d.k_norm = kn.ptr<float>(); d.eps = a->eps;
+    d.rope = rope.ptr<float>(); d.pos = pos.ptr<int>();
+    d.kc = kc.b.ptr<uint16_t>(); d.vc = vc.b.ptr<uint16_t>(); d.vt = vt.b.ptr<uint16_t>();
+    d.B = B; d.n_head = nh; d.n_kv_head = nkv; d.max_ctx = a->max_ctx; d.scale = a->scale; d.kv_nt = a->kv_nt;
+    KtFenced *state[5] = {&kc, &vc, &vt, &k8, &v8};
+    const void *given[5] = {hk.data(), hv.data(), a->vt, a->k8, a->v8};
+    const char *name[5] = {"kc", "vc", "vt", "k8", "v8"};
+    std::string tag, msg;
+    bool declined = false;
+    for (int r = 0; r < a->repeat && !declined; r++) {
+        if (r)   // the caches and shadows as the caller gave them
+            for (int i = 0; i < 5; i++) HIPCHK(hipMemcpy(state[i]->b.ptr<char>(), given[i], state[i]->bytes, hipMemcpyHostToDevice));
+        d.out = o16[r].ptr<uint16_t>(); d.out32 = o32[r].ptr<float>(); d.outq = oq[r].ptr<int8_t>(); d.outd = od[r].ptr<float>();
+        const bool ran = launch_decode_attention_fp8(d, k8.b.ptr<uint8_t>(), v8.b.ptr<uint8_t>(), a->exp, nullptr);
+        declined = take_declined(&msg) || !ran;
+        if (!declined && !take_kernel(&tag)) return fail(QASR_ERR_STATE, "the launcher recorded no kernel tag");
+        int32_t unused = 0;
+        if ((rc = finish_plain(&unused, true))) return rc;
+        for (int i = 0; i < 5; i++) {
+            std::vector<unsigned char> &dst = r ? last[i] : first[i];
+            dst.resize(state[i]->bytes);
+            if ((rc = state[i]->take(dst.data(), name[i]))) return rc;
+        }
+    }
+    a->declined = declined;
+    if (declined && msg.empty()) msg = "the launcher returned false";
+    copy_str(a->tag, sizeof a->tag, declined ? std::string() : tag);
+    copy_str(a->msg, sizeof a->msg, msg);
+    if (memcmp(first[0].data() + kv, hk.data() + kv, padded - kv) || memcmp(first[1].data() + kv, hv.data() + kv, padded - kv))
+        return fail(QASR_ERR_STATE, "a write into the rows after the last K / V region");
+    if (two && !declined)
+        for (int i = 0; i < 5; i++)
+            if (first[i] != last[i]) return fail(QASR_ERR_STATE, std::string("the two launches left different ") + name[i]);
+    memcpy(a->kc, first[0].data(), kv);
+    memcpy(a->vc, first[1].data(), kv);
+    memcpy(a->vt, first[2].data(), vtb);
+    memcpy(a->k8, first[3].data(), s8);
+    memcpy(a->v8, first[4].data(), s8);
+    for (int r = 0; r < a->repeat; r++)
+        if ((rc = get(o16[r], h16[r])) || (rc = get(o32[r], h32[r])) || (rc = get(oq[r], hq[r])) || (rc = get(od[r], hd[r]))) return rc;
+    return 0;
+}
+
 // ------------------------------------------------------------- conv front end
 // (tests/test_gpu_conv_kernels.py) launch_conv1 and launch_gemm's AM_CONV2 / AM_CONV3 on a caller-supplied chunk
 // table.  The input sits between guard_in elements of 0xFF bytes on both sides: the NHWC layout puts a neighbour's

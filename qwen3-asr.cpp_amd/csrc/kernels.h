@@ -394,6 +394,10 @@ struct FuseCfg {
                                         // GEMV (gemv_rows.hip / gemv_rows_q8.hip): 0 never, 1 in decoders with hidden >= 2048 at
                                         // the (launch, rows) pairs where it measured faster (engine_decode.hip kRowsAuto /
                                         // kRowsAutoQ8), 2 wherever it covers
+    int kv_fp8 = 0;                     // 1: an E4M3 shadow of the K / V caches (kv_fp8.hip) kept beside them, read by the
+                                        // decode attention of 9 .. 128-row steps (decode_attn_seq_fp8_kernel) whatever
+                                        // fa_exact_decode, att_stream and fx_seq say; 0: no allocation, no launch, nothing changes
+    int kv_fp8_exp = 0;                 // the shadow's exponent s, -8 .. 8: bytes hold RNE_E4M3FN(clamp(x 2^s, -448, 448))
     unsigned int *err = nullptr;        // sticky device error word (DevErr bits)
 };
 // co-resident workgroup capacity of the fused kernels on the current device
@@ -582,6 +586,34 @@ int decode_max_splits();
 // splits per (sequence, kv group) of the launch launch_decode_attention makes of a (B, n_kv_head, grid_splits, spl1,
 // spl_batch, stream_blocks); 0 = the per-sequence kernel
 int decode_split_count(const DecodeAttnArgs &a);
+
+// ---------------------------------------------------------------- FP8 shadow KV cache (kv_fp8.hip)
+// k8 / v8: E4M3 bytes in the fp16 caches' layout [layers][slots][n_kv_head][max_ctx][128], derived from kc / vc by the
+// rule of kv_fp8_host.h with exponent `exp`.  The fp16 caches stay the source of truth; there is no V^T shadow.
+// kv_fp8_convert_kernel: row b of the launch re-derives positions [f, e) of slot (slot ? slot[b] : b), every layer and
+// kv head: f = from ? from[b] : 0, e = to ? to[b] : f + (len ? len[b] : span), both clamped to [0, max_ctx].  The
+// arrays are device memory read by the kernel (a captured step replays it with the values of that step); the grid
+// covers `span` positions from f on, so span must reach the longest range the launch can meet.  Nothing outside the
+// ranges is written; an empty range writes nothing.
+struct KvFp8ConvertArgs {
+    const uint16_t *kc, *vc;
+    uint8_t *k8, *v8;
+    int layers, slots, n_kv_head, max_ctx;
+    const int *slot, *from, *to, *len;
+    int B, span, exp;
+};
+bool launch_kv_fp8_convert(const KvFp8ConvertArgs &a, hipStream_t s);   // false = bad shape, nothing launched
+// decode_attn_seq_fp8_kernel: the per-sequence decode attention (one workgroup a (kv group, sequence), both query
+// heads) reading the shadow's bytes for the keys below pos.  It writes the new token's fp16 K / V / V^T rows with
+// decode_attn_seq_kernel's bits and the shadow's rows at pos by the rule, and attends the rounded new row, so the
+// output is a function of q and the shadow alone: f16 MFMA scores and fp32 online softmax and P.V over
+// float(q) * 2^-exp, the arithmetic of launch_decode_attention's per-sequence kernel on those keys.  Reads of a: qkv,
+// q_norm, k_norm, eps, rope, pos, kc, vc, vt, B, n_head, n_kv_head, max_ctx, scale, kv_nt, stamp and one of out /
+// out32 / outq + outd; k8 / v8 are this layer's shadow bases.  Shadow rows above pos are never loaded; row pos is
+// loaded as the shadow holds it (any bytes) and replaced in registers.  Takes n_head == 2 * n_kv_head, B >= 1,
+// |exp| <= 8; anything else is declined (note_declined_shape), nothing launched, false returned.
+bool decode_attention_fp8_covers(int n_head, int n_kv_head);
+bool launch_decode_attention_fp8(const DecodeAttnArgs &a, uint8_t *k8, uint8_t *v8, int exp, hipStream_t s);
 
 // ---------------------------------------------------------------- decoder misc
 // embedding gather (fp16 -> fp32) + audio splice (src/text_decoder.cpp:429-459)

@@ -77,6 +77,9 @@ static void usage(const char *prog) {
     fprintf(stderr, "  --top-k <n>            The n (1..8) most likely tokens of every step; with --tokens, listed under each token\n");
     fprintf(stderr, "  --beam-width <n>       Beam search of width n (2..8) instead of greedy decoding\n");
     fprintf(stderr, "  --beams                With --beam-width: list every hypothesis with its summed log-probability\n");
+    fprintf(stderr, "  --kv-fp8               Decode batches of 9..128 rows attend an FP8 (E4M3) shadow of the KV cache: half the cache\n");
+    fprintf(stderr, "                         bytes a step, fp32-softmax numerics on rounded keys (not ggml's chain); off by default\n");
+    fprintf(stderr, "  --kv-fp8-exp <n>       With --kv-fp8: the shadow stores x * 2^n (-8..8, default 0)\n");
     fprintf(stderr, "  --temperature <T>      Sample every token from softmax(logits / T), 0 < T <= 100, instead of greedy decoding\n");
     fprintf(stderr, "  --min-p <p>            With --temperature: only tokens at least p (0..1) times as probable as the greedy one\n");
     fprintf(stderr, "  --seed <n>             With --temperature: the 64-bit seed of the draws (default: 0)\n");
@@ -180,6 +183,13 @@ static bool parse(int argc, char **argv, cli_params &p) {
             if (p.beam_width < 2 || p.beam_width > 8) { fprintf(stderr, "Error: --beam-width takes 2..8\n"); return false; }
         }
         else if (!strcmp(a, "--beams")) p.beams = true;
+        // the FP8 shadow KV cache: every context this process creates takes the options' environment defaults
+        else if (!strcmp(a, "--kv-fp8")) setenv("QASR_KV_FP8", "1", 1);
+        else if (!strcmp(a, "--kv-fp8-exp")) {
+            if (!val(v)) return false;
+            if (atoi(v.c_str()) < -8 || atoi(v.c_str()) > 8) { fprintf(stderr, "Error: --kv-fp8-exp takes -8..8\n"); return false; }
+            setenv("QASR_KV_FP8_EXP", v.c_str(), 1);
+        }
         else if (!strcmp(a, "--temperature")) {
             if (!val(v)) return false;
             p.temperature = (float)atof(v.c_str());

@@ -597,11 +597,16 @@ def _guarded_fetch(fetch, failed: list):
 class Context:
     """qasr_ctx: stream, KV cache, scratch (TextDecoder::init_kv_cache analogue)."""
 
-    def __init__(self, model: Model, max_batch: int = 1, max_ctx: int = 2048):
+    def __init__(self, model: Model, max_batch: int = 1, max_ctx: int = 2048, kv_fp8: int = 0, kv_fp8_exp: int = 0):
+        """kv_fp8 / kv_fp8_exp: the context options of those names (the FP8 shadow KV cache), set when non-zero"""
         self.model = model
         self.h = C.c_void_p()
         _check(lib().qasr_ctx_create(model.h, max_batch, max_ctx, C.byref(self.h)), "qasr_ctx_create")
         self.max_batch, self.max_ctx = max_batch, max_ctx
+        if kv_fp8_exp:
+            self.set_option("kv_fp8_exp", kv_fp8_exp)
+        if kv_fp8:
+            self.set_option("kv_fp8", kv_fp8)
 
     def close(self):
         if self.h:
