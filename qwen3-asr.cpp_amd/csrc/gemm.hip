@@ -19,7 +19,7 @@
 #include "gemm_epi.h"
 #include "gemm8p.h"
 #include "gemm_glds.h"
-#include "q8_prologue.h"
+#include "act_prologue.h"
 
 namespace qasr {
 
@@ -579,32 +579,13 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(GemvArgs g) {
                 }
     };
     if (cg < ncg) wload(cg);
-    // ---- prologue: each thread owns 4 consecutive elements per 1024-wide pass
     constexpr int KP = NK;
-    {   // q8_prologue.h: the arithmetic and the thread-to-element map
+    {   // ---- prologue (act_prologue.h: the arithmetic and the thread-to-element map)
         float4 xr[MR][KP];
-        double ss[MR];
+        xp_load_rows(g, red, xr);
 #pragma unroll
         for (int m = 0; m < MR; m++) {
-            ss[m] = 0.0;
-#pragma unroll
-            for (int p = 0; p < KP; p++) {
-                const int k = p * 1024 + tid * 4;
-                xr[m][p] = m < g.M && k < K ? q8p_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                q8p_sq(ss[m], xr[m][p]);
-            }
-        }
-        if (g.norm_w) {
-#pragma unroll
-            for (int m = 0; m < MR; m++) {
-                const double t = wave_sum_d(ss[m]);
-                if (lane == 0) red[wid][m] = t;
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int m = 0; m < MR; m++) {
-            const float scale = q8p_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
+            const float scale = xp_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
 #pragma unroll
             for (int p = 0; p < KP; p++) {
                 const int k = p * 1024 + tid * 4;

@@ -26,11 +26,7 @@
 //            result is a function of the operands alone.
 //
 // Registers, LDS and occupancy of every instantiation: profiles/gemv_rows/resources.txt.
-#include <type_traits>
-
-#include "dev_common.h"
-#include "gemm_epi.h"
-#include "kernels.h"
+#include "gemv_rows_core.h"
 
 namespace qasr {
 
@@ -67,79 +63,11 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(GemvArgs g) {
     int t = blockIdx.x, r = 0, j = 0;
     wload(std::integral_constant<int, 0>{}, t, r, j);
 
-    // ---- x rows -> fp16 in LDS.  Thread tid owns elements p * 1024 + 4 tid .. + 3 of every row (gemv_kernel's map)
+    // ---- x rows -> fp16 in LDS (act_prologue.h: gemv_kernel's arithmetic and thread-to-element map)
     if (g.norm_w || g.x || g.embd_ids) {
-        auto xload = [&](int m, int k) {
-            if (g.embd_ids) {
-                const uint2 hv = *(const uint2 *)(g.embd + (long)g.embd_ids[m] * K + k);
-                return make_float4(u16_to_f(hv.x & 0xffff), u16_to_f(hv.x >> 16), u16_to_f(hv.y & 0xffff), u16_to_f(hv.y >> 16));
-            }
-            return *(const float4 *)(g.x + (long)m * g.ldx + k);
-        };
-        auto sq = [](double &ss, const float4 &v) {
-            ss += (double)(v.x * v.x);
-            ss += (double)(v.y * v.y);
-            ss += (double)(v.z * v.z);
-            ss += (double)(v.w * v.w);
-        };
-        auto xput = [&](int m, int k, const float4 &v, float scale) {
-            float e[4] = {v.x, v.y, v.z, v.w};
-            if (g.norm_w) {
-                const float4 w = *(const float4 *)(g.norm_w + k);
-                e[0] = fmul_rn(fmul_rn(e[0], scale), w.x); e[1] = fmul_rn(fmul_rn(e[1], scale), w.y);
-                e[2] = fmul_rn(fmul_rn(e[2], scale), w.z); e[3] = fmul_rn(fmul_rn(e[3], scale), w.w);
-            }
-            *(uint2 *)(xs + gr_off(m, k, K)) = make_uint2(f_to_u16(e[0]) | ((uint32_t)f_to_u16(e[1]) << 16),
-                                                           f_to_u16(e[2]) | ((uint32_t)f_to_u16(e[3]) << 16));
-            if (g.embd_ids && g.x_store && blockIdx.x == 0) *(float4 *)(g.x_store + (long)m * g.ldx + k) = v;
-        };
-        auto row_scale = [&](int m) {
-            if (!g.norm_w) return 1.0f;
-            const double tot = red[0][m] + red[1][m] + red[2][m] + red[3][m];
-            return 1.0f / sqrtf((float)(tot / K) + g.eps);
-        };
-        if (K <= 2048) {   // the rows stay in registers between the sum and the scaling (the hidden-2048 decoders)
-            float4 xr[8][2];
-#pragma unroll
-            for (int m = 0; m < 8; m++) {
-                double ss = 0.0;
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    const int k = p * 1024 + tid * 4;
-                    xr[m][p] = m < M && k < K ? xload(m, k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    sq(ss, xr[m][p]);
-                }
-                if (g.norm_w) {
-                    ss = wave_sum_d(ss);
-                    if (lane == 0) red[wid][m] = ss;
-                }
-            }
-            if (g.norm_w) __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 8; m++) {
-                if (m >= M) break;
-                const float scale = row_scale(m);
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    const int k = p * 1024 + tid * 4;
-                    if (k < K) xput(m, k, xr[m][p], scale);
-                }
-            }
-        } else {           // longer rows are read twice (the second time from the caches)
-            if (g.norm_w) {
-                for (int m = 0; m < M; m++) {
-                    double ss = 0.0;
-                    for (int k = tid * 4; k < K; k += 1024) sq(ss, xload(m, k));
-                    ss = wave_sum_d(ss);
-                    if (lane == 0) red[wid][m] = ss;
-                }
-                __syncthreads();
-            }
-            for (int m = 0; m < M; m++) {
-                const float scale = row_scale(m);
-                for (int k = tid * 4; k < K; k += 1024) xput(m, k, xload(m, k), scale);
-            }
-        }
+        xp_rows(g, red, [&](int m, int k, const float4 &v, float scale) {
+            *(uint2 *)(xs + gr_off(m, k, K)) = xp_f16x4(g, v, k, scale);
+        });
     } else {
         for (int k = tid * 8; k < K; k += 256 * 8)
             for (int m = 0; m < M; m++) *(u32x4 *)(xs + gr_off(m, k, K)) = *(const u32x4 *)(g.xh + (long)m * g.ldxh + k);
@@ -221,40 +149,15 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(GemvArgs g) {
     stamp_end(g.stamp);
 }
 
-// static LDS of an instantiation (red + part), for the workgroups a CU holds
-static constexpr int gr_static_lds(int epi) { return 4 * 8 * 8 + 2 * 3 * (epi == EPI_SWIGLU_F16 ? 2 : 1) * 64 * 16; }
-
-template <int EPI, int CH>
-static void run_gemv_rows(const GemvArgs &g, hipStream_t s) {
-    static int ncu_dev[64];   // per device: CU count once the LDS attribute is set (rows above 64 KiB need it)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int &ncu = ncu_dev[dev & 63];
-    if (!ncu) {
-        int n = 0;
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipFuncSetAttribute((const void *)gemv_rows_kernel<EPI, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192 * 2);
-        ncu = n > 0 ? n : 256;
-    }
-    // every tile's workgroup resident at once where the CUs hold them: two a CU by registers (two chunk buffers of
-    // up to 64 VGPRs), fewer by LDS (160 KiB a CU); the grid strides over the tiles beyond
-    const int lds = g.M * g.K * 2, fit = (160 * 1024) / (lds + gr_static_lds(EPI));
-    const int cap = ncu * (fit < 1 ? 1 : fit > 2 ? 2 : fit), ntiles = (g.N + 15) / 16;
-    note_kernel("gemv_rows", 2, EPI, CH);
-    hipLaunchKernelGGL((gemv_rows_kernel<EPI, CH>), dim3(ntiles < cap ? ntiles : cap), dim3(256), lds, s, g);
-}
-
 template <int EPI>
 static void gemv_rows_ch(const GemvArgs &g, hipStream_t s) {
-    // MFMA steps a chunk: a wave's quarter K / 4 is whole chunks of 32 CH elements
-    if (g.K % 2048 == 0) run_gemv_rows<EPI, 16>(g, s);
-    else if (g.K % 1024 == 0) run_gemv_rows<EPI, 8>(g, s);
-    else run_gemv_rows<EPI, 2>(g, s);
+    rows_chunk_ladder(g.K, [&](auto ch) {   // MFMA steps a chunk
+        constexpr int CH = decltype(ch)::value;
+        run_rows<gemv_rows_kernel<EPI, CH>>(g, s, g.M * g.K * 2, rows_static_lds(EPI == EPI_SWIGLU_F16 ? 2 : 1), 8 * 8192 * 2, "gemv_rows", EPI, CH);
+    });
 }
 
-// What launch_gemv_rows takes: f16 W rows K apart (no Wd), 2 <= M <= 8, K % 256 == 0, 256 <= K <= 8192, any N
-// (the weights within the descriptor's 32-bit range), the input by launch_gemv's rules (fp32 x / the gathered
-// embd rows with ldx % 4 == 0, optionally norm_w; else xh with ldxh % 8 == 0), and
+// What launch_gemv_rows takes: f16 W rows K apart (no Wd), rows_shape_ok's shapes and inputs, and
 //   EPI_F32         + bias, + res (out_f32 may be res)
 //   EPI_F16         + bias
 //   EPI_SWIGLU_F16  N % 16 == 0, gemv1_kernel's 16-row gate / up interleave; no bias, no res
@@ -262,15 +165,7 @@ static void gemv_rows_ch(const GemvArgs &g, hipStream_t s) {
 // among it -- is declined: recorded (note_declined / note_declined_shape), nothing launched or written.
 bool gemv_rows_covers(int epi, const GemvArgs &g) {
     if (epi != EPI_F32 && epi != EPI_F16 && epi != EPI_SWIGLU_F16) return false;
-    if (g.M < 2 || g.M > 8 || g.N < 1 || !g.W || g.Wd || g.amax) return false;
-    if (g.K % 256 != 0 || g.K < 256 || g.K > 8192) return false;
-    const int nr = epi == EPI_SWIGLU_F16 ? 2 : 1;
-    if ((unsigned long long)g.N * nr * g.K * 2 > 0xffff0000ull) return false;
-    if (g.norm_w || g.x || g.embd_ids) {
-        if (!(g.embd_ids ? g.embd != nullptr : g.x != nullptr) || g.ldx % 4 != 0 || g.ldx < g.K) return false;
-    } else if (!g.xh || g.ldxh % 8 != 0 || g.ldxh < g.K) {
-        return false;
-    }
+    if (g.Wd || !rows_shape_ok(g, epi == EPI_SWIGLU_F16 ? 2 : 1, 2)) return false;
     switch (epi) {
         case EPI_F32: return g.out_f32 && g.ldo >= g.N && (!g.res || g.ldr >= g.N);
         case EPI_F16: return g.out_f16 && !g.res && g.ldo16 >= g.N;
@@ -279,11 +174,8 @@ bool gemv_rows_covers(int epi, const GemvArgs &g) {
 }
 
 bool launch_gemv_rows(int epi, const GemvArgs &g, hipStream_t s) {
-    if (!gemv_rows_covers(epi, g)) {
-        if (epi != EPI_F32 && epi != EPI_F16 && epi != EPI_SWIGLU_F16) note_declined("launch_gemv_rows", 0, epi);
-        else note_declined_shape("launch_gemv_rows", g.M, g.N, g.K);
-        return false;
-    }
+    if (!gemv_rows_covers(epi, g))
+        return rows_declined("launch_gemv_rows", epi == EPI_F32 || epi == EPI_F16 || epi == EPI_SWIGLU_F16, epi, g);
     switch (epi) {
         case EPI_F32: gemv_rows_ch<EPI_F32>(g, s); break;
         case EPI_F16: gemv_rows_ch<EPI_F16>(g, s); break;

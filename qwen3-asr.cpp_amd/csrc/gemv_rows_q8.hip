@@ -19,7 +19,7 @@
 //   scales   the fp16 block scales the lane needs on the C layout (weight rows 4 q .. 4 q + 3, the chunk's CB
 //            blocks: CB / 2 dwords a row) are requested with the chunk's weights through a second descriptor
 //            and ride in the same two buffers; the 16 lanes of a q share each address.
-//   x        prepared once a workgroup with q8_prologue.h (gemv_q8_kernel's arithmetic and thread-to-element map:
+//   x        prepared once a workgroup with act_prologue.h (gemv_q8_kernel's arithmetic and thread-to-element map:
 //            the same quants and scales): int8 in LDS [M][K], 16-byte piece p of row r at piece p ^ (r & 15) (rows
 //            are a multiple of 256 B apart: the row lanes of a B fragment would otherwise share a bank group), the
 //            fp32 block scales behind them as [K / 32][8] (a fragment's rows on consecutive banks).  Lanes whose row
@@ -31,12 +31,7 @@
 //
 // The other operand form -- 8-byte loads, one v_mfma_i32_16x16x32_i8 a block -- and what was measured: DESIGN.md 5.13.
 // Registers, LDS and occupancy of every instantiation: profiles/gemv_rows_q8/resources.txt.
-#include <type_traits>
-
-#include "dev_common.h"
-#include "gemm_epi.h"
-#include "kernels.h"
-#include "q8_prologue.h"
+#include "gemv_rows_core.h"
 
 namespace qasr {
 
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256) void gemv_rows_q8_kernel(GemvArgs g) {
     int t = blockIdx.x, r = 0, j = 0;
     wload(std::integral_constant<int, 0>{}, t, r, j);
 
-    // ---- x rows -> Q8_0 in LDS.  Thread tid owns elements p * 1024 + 4 tid .. + 3 of every row (q8_prologue.h)
+    // ---- x rows -> Q8_0 in LDS.  Thread tid owns elements p * 1024 + 4 tid .. + 3 of every row (act_prologue.h)
     {
         auto xput = [&](int m, int k, const float4 &v, float scale) {   // every lane of the wave, k < K or not
             float d;
@@ -111,8 +106,8 @@ __global__ __launch_bounds__(256) void gemv_rows_q8_kernel(GemvArgs g) {
 #pragma unroll
                 for (int p = 0; p < 2; p++) {
                     const int k = p * 1024 + tid * 4;
-                    xr[m][p] = m < M && k < K ? q8p_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    q8p_sq(ss, xr[m][p]);
+                    xr[m][p] = m < M && k < K ? xp_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    xp_sq(ss, xr[m][p]);
                 }
                 if (g.norm_w) {
                     ss = wave_sum_d(ss);
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(256) void gemv_rows_q8_kernel(GemvArgs g) {
 #pragma unroll
             for (int m = 0; m < 8; m++) {
                 if (m >= M) break;
-                const float scale = q8p_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
+                const float scale = xp_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
 #pragma unroll
                 for (int p = 0; p < 2; p++) xput(m, p * 1024 + tid * 4, xr[m][p], scale);
             }
@@ -132,17 +127,17 @@ __global__ __launch_bounds__(256) void gemv_rows_q8_kernel(GemvArgs g) {
             if (g.norm_w) {
                 for (int m = 0; m < M; m++) {
                     double ss = 0.0;
-                    for (int k = tid * 4; k < K; k += 1024) q8p_sq(ss, q8p_load(g, m, k));
+                    for (int k = tid * 4; k < K; k += 1024) xp_sq(ss, xp_load(g, m, k));
                     ss = wave_sum_d(ss);
                     if (lane == 0) red[wid][m] = ss;
                 }
                 __syncthreads();
             }
             for (int m = 0; m < M; m++) {
-                const float scale = q8p_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
+                const float scale = xp_row_scale(g, red[0][m], red[1][m], red[2][m], red[3][m]);
                 for (int p = 0; p < np; p++) {
                     const int k = p * 1024 + tid * 4;
-                    xput(m, k, k < K ? q8p_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f), scale);
+                    xput(m, k, k < K ? xp_load(g, m, k) : make_float4(0.f, 0.f, 0.f, 0.f), scale);
                 }
             }
         }
@@ -239,64 +234,34 @@ __global__ __launch_bounds__(256) void gemv_rows_q8_kernel(GemvArgs g) {
     stamp_end(g.stamp);
 }
 
-// LDS of a launch: the rows, their scales, and the static part (red + part)
-static constexpr int grq_static_lds(int epi) { return 4 * 8 * 8 + 2 * 3 * (epi == EPI_SWIGLU_F32 ? 2 : 1) * 64 * 16; }
+// dynamic LDS of a launch: the rows and their scales
 static int grq_dynamic_lds(int M, int K) { return M * K + (K / 32) * 8 * 4; }
-
-template <int EPI, int CB>
-static void run_gemv_rows_q8(const GemvArgs &g, hipStream_t s) {
-    static int ncu_dev[64];   // per device: CU count once the LDS attribute is set (rows above 64 KiB need it)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int &ncu = ncu_dev[dev & 63];
-    if (!ncu) {
-        int n = 0;
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipFuncSetAttribute((const void *)gemv_rows_q8_kernel<EPI, CB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  grq_dynamic_lds(8, 8192));
-        ncu = n > 0 ? n : 256;
-    }
-    // every tile's workgroup resident at once where the CUs hold them: two a CU by registers, fewer by LDS (160 KiB a
-    // CU); the grid strides over the tiles beyond
-    const int lds = grq_dynamic_lds(g.M, g.K), fit = (160 * 1024) / (lds + grq_static_lds(EPI));
-    const int cap = ncu * (fit < 1 ? 1 : fit > 2 ? 2 : fit), ntiles = (g.N + 15) / 16;
-    note_kernel("gemv_rows_q8", 2, EPI, CB);
-    hipLaunchKernelGGL((gemv_rows_q8_kernel<EPI, CB>), dim3(ntiles < cap ? ntiles : cap), dim3(256), lds, s, g);
-}
 
 template <int EPI>
 static void gemv_rows_q8_cb(const GemvArgs &g, hipStream_t s) {
-    // Q8_0 blocks a chunk: a wave's quarter K / 4 is whole chunks of 32 CB elements
-    if (g.K % 2048 == 0) run_gemv_rows_q8<EPI, 16>(g, s);
-    else if (g.K % 1024 == 0) run_gemv_rows_q8<EPI, 8>(g, s);
-    else run_gemv_rows_q8<EPI, 2>(g, s);
+    rows_chunk_ladder(g.K, [&](auto cb) {   // Q8_0 blocks a chunk
+        constexpr int CB = decltype(cb)::value;
+        run_rows<gemv_rows_q8_kernel<EPI, CB>>(g, s, grq_dynamic_lds(g.M, g.K), rows_static_lds(EPI == EPI_SWIGLU_F32 ? 2 : 1),
+                                               grq_dynamic_lds(8, 8192), "gemv_rows_q8", EPI, CB);
+    });
 }
 
-// What launch_gemv_rows_q8 takes: Q8_0 W (int8 rows K apart, fp16 scales Wd [rows][K / 32]), 2 <= M <= 8,
-// K % 256 == 0, 256 <= K <= 8192, any N (the weights within the descriptor's 32-bit range), fp32 x or the gathered
-// embd rows (+ x_store) with ldx % 4 == 0 and ldx >= K, optionally norm_w -- launch_gemv's Q8_0 rules -- and
+// What launch_gemv_rows_q8 takes: Q8_0 W (int8 rows K apart, fp16 scales Wd [rows][K / 32]), rows_shape_ok's shapes,
+// fp32 x or the gathered embd rows (+ x_store), optionally norm_w -- launch_gemv's Q8_0 rules -- and
 //   EPI_F32         + bias, + res (out_f32 may be res)
 //   EPI_SWIGLU_F32  N % 16 == 0, the 16-row gate / up interleave; no bias, no res
 // with trace / stamp / zero8 honoured.  Everything else -- f16 weights (no Wd), xh input, EPI_ARGMAX and the fp16
 // epilogues, M = 1, M > 8 among it -- is declined: recorded (note_declined / note_declined_shape), nothing launched.
 bool gemv_rows_q8_covers(int epi, const GemvArgs &g) {
     if (epi != EPI_F32 && epi != EPI_SWIGLU_F32) return false;
-    if (g.M < 2 || g.M > 8 || g.N < 1 || !g.W || !g.Wd || g.amax || g.xh) return false;
-    if (g.K % 256 != 0 || g.K < 256 || g.K > 8192) return false;
-    const int nr = epi == EPI_SWIGLU_F32 ? 2 : 1;
-    if ((unsigned long long)g.N * nr * g.K > 0xffff0000ull) return false;
-    if (!(g.embd_ids ? g.embd != nullptr : g.x != nullptr) || g.ldx % 4 != 0 || g.ldx < g.K) return false;
+    if (!g.Wd || g.xh || !rows_shape_ok(g, epi == EPI_SWIGLU_F32 ? 2 : 1, 1)) return false;
     if (!g.out_f32 || g.ldo < g.N) return false;
     if (epi == EPI_F32) return !g.res || g.ldr >= g.N;
     return !g.res && !g.bias && g.N % 16 == 0;
 }
 
 bool launch_gemv_rows_q8(int epi, const GemvArgs &g, hipStream_t s) {
-    if (!gemv_rows_q8_covers(epi, g)) {
-        if (epi != EPI_F32 && epi != EPI_SWIGLU_F32) note_declined("launch_gemv_rows_q8", 0, epi);
-        else note_declined_shape("launch_gemv_rows_q8", g.M, g.N, g.K);
-        return false;
-    }
+    if (!gemv_rows_q8_covers(epi, g)) return rows_declined("launch_gemv_rows_q8", epi == EPI_F32 || epi == EPI_SWIGLU_F32, epi, g);
     if (epi == EPI_F32) gemv_rows_q8_cb<EPI_F32>(g, s);
     else gemv_rows_q8_cb<EPI_SWIGLU_F32>(g, s);
     return true;

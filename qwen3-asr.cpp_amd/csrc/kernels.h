@@ -251,6 +251,7 @@ bool launch_score_head(const ScoreHeadArgs &a, hipStream_t s);   // false = shap
 
 // skinny (decode) path: M <= 8 rows, weights streamed once from HBM.
 // x is fp32 [M][K]; if norm_w != nullptr the rows are RMS-normalised first
+// (launch_gemv_rows reads norm_w 16 bytes at a time: 16-byte aligned, as the arena's are)
 // (ggml_rms_norm + ggml_mul), then rounded to fp16 as ggml's mul_mat does.
 struct GemvArgs {
     const float *x; int ldx;
@@ -306,7 +307,7 @@ bool launch_gemv_wide(int epi, const GemvArgs &g, hipStream_t s);
 bool gemv_rows_covers(int epi, const GemvArgs &g);
 bool launch_gemv_rows(int epi, const GemvArgs &g, hipStream_t s);
 // gemv_rows_q8.hip: the same for Q8_0 weights, on v_mfma_i32_16x16x64_i8 (one block's exact integer dots an MFMA),
-// the rows normed and quantised in the launch with gemv_q8_kernel's prologue (q8_prologue.h): launch_gemv's products
+// the rows normed and quantised in the launch with gemv_q8_kernel's prologue (act_prologue.h): launch_gemv's products
 // in another fp32 summation order.  Declines and gemv_rows_q8_covers as above
 bool gemv_rows_q8_covers(int epi, const GemvArgs &g);
 bool launch_gemv_rows_q8(int epi, const GemvArgs &g, hipStream_t s);
